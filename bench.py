@@ -850,6 +850,48 @@ def host_modes_report(rows, H, W):
     return out
 
 
+# ---- --dump-outputs ------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # everything --dump-outputs writes together, .npy headers included
+DUMP_SEED = 20241015              # the pixel sample of outputs larger than the limit: the same positions in every run
+
+
+def dump_outputs(out_dir, images, small):
+    """Writes the results of the timed path as out_dir/<name>.npy so that two builds can be compared output for output.
+
+    images: name -> host array of shape (H, W) or (H, W, C), every one of the same H x W (the flow, the warped image);
+    small: name -> host array written whole (level reports, affine matrix).  Floating results keep float32 / float64,
+    integer images become float32 (exact for uint8 / uint16).  When the whole images do not fit DUMP_LIMIT_BYTES, every
+    image is written at the same seeded sample of pixel positions instead, in row-major order: shape (n,) or (n, C).
+    Returns what was written, for the JSON line."""
+    import numpy as np
+
+    def as_float(a):
+        return np.asarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+
+    small = {k: as_float(np.asarray(v)) for k, v in small.items()}
+    hw = {a.shape[:2] for a in images.values()}
+    if len(hw) > 1:
+        raise ValueError(f"--dump-outputs: image outputs of different sizes {sorted(hw)}")
+    H, W = hw.pop() if hw else (0, 0)
+    px_bytes = sum(int(np.prod(a.shape[2:], dtype=np.int64)) * (8 if a.dtype == np.float64 else 4) for a in images.values())
+    room = DUMP_LIMIT_BYTES - sum(v.nbytes for v in small.values()) - 256 * (len(images) + len(small))
+    sample = None
+    if H * W * px_bytes > room:
+        n = min(H * W, room // max(px_bytes, 1))
+        sample = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, size=n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, a in list(images.items()) + list(small.items()):
+        if name in images:
+            a = a if sample is None else a.reshape((H * W,) + a.shape[2:])[sample]
+            a = as_float(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        files[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return {"dir": out_dir, "files": files, "image_shape": [H, W],
+            "sample": None if sample is None else {"pixels": int(sample.size), "seed": DUMP_SEED,
+                                                    "how": "the same seeded positions in every image, row-major order"}}
+
+
 # ---- launcher ----------------------------------------------------------------------------------------------
 def free_port():
     s = socket.socket()
@@ -978,7 +1020,14 @@ def main():
                          "has been gathered by then)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / reduce plumbing only, no GPU work (CPU test of the N-rank launcher)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what its last pair of the last step computed -- flow, warped "
+                         "image, level reports (factor, mi_after, mi_before, accepted) and, with --feature-init, the affine "
+                         "matrix -- as DIR/<name>.npy (float32 / float64; images larger than 64 MB in all as a fixed, seeded "
+                         "pixel sample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -1146,13 +1195,15 @@ def main():
     warper = Warper()
     warper.tile_size, warper.overlap = reg.tile_size, reg.overlap
 
+    last_tmat = [None]   # FeatureRegistrator's matrix of the last pair, for --dump-outputs
+
     def one_pair(dref, dmov, inv_affine, host):
         if freg is not None:
             # the pair is resident in HBM when the timed region starts (the metric's rule for every workload): the affine
             # initialisation reads the same device arrays the optical-flow stage reads; --feature-init-from-host times the
             # numpy entry instead (+ the upload of both images: 2 x 64 MB, ~3 ms)
             freg.ref_img, freg.mov_img = host if args.feature_init_from_host else (dref, dmov)
-            t_mat = freg.register()
+            t_mat = last_tmat[0] = freg.register()
             m = ctx.warp_affine(dmov, np.linalg.pinv(np.vstack([t_mat, [0, 0, 1]])))
         else:
             m = dmov if inv_affine is None else ctx.warp_affine(dmov, inv_affine)   # transform_img_with_tmat (utils.py:98-114)
@@ -1214,6 +1265,17 @@ def main():
         "pairs": my_pairs, "ms_per_step": round((t1 - t0) / args.steps * 1e3, 3), "clock_ghz": round(clock_ghz, 3),
         "result": summary})
     gather_ms = (time.perf_counter() - tg0) * 1e3
+    dumped = None
+    if args.dump_outputs and rank == 0 and out is not None:
+        # downloaded into pageable arrays that are dropped right away: the context's page-locked pool stays as it was for the
+        # informational legs (flow, warped: the summary's names for `out`)
+        images = {"flow": flow.numpy(out=np.empty(flow.shape, flow.dtype)),
+                  "warped": warped.numpy(out=np.empty(warped.shape, warped.dtype))}
+        small = {"levels": np.array([[r.factor, r.mi_after, r.mi_before, r.accepted] for r in reg.level_reports], np.float64)}
+        if last_tmat[0] is not None:
+            small["affine_tmat"] = np.asarray(last_tmat[0], np.float64)
+        dumped = dump_outputs(args.dump_outputs, images, small)
+        del images
     # ---- informational legs of a multi-rank run.  The headline's rows are on rank 0; nothing below enters a torch.distributed
     # collective after the one broadcast of rank 0's decisions: barriers and rows go through SoftSync, every wait bounded.
     host_rows_all, host_skip, shared_ms, shared_note, soft = None, None, None, None, None
@@ -1338,6 +1400,8 @@ def main():
             "results_to_shared_array_ms": round(shared_ms, 1) if shared_ms is not None else None,
             "results_to_shared_array": shared_note,
         }
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         if host_skip:
             res["host_modes"] = {"skipped": host_skip}
         if host_rows_all is not None:
