@@ -138,6 +138,13 @@ SIGNATURES.update({
     "ma_convert_f32": (_i, [_vp, _vp, _i, _sz, _vp]),
 })
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_qc.h (registration quality maps)
+QC_SIGNATURES = {
+    "ma_qc_nmi_grid": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "ma_qc_flow_grid": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_d), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                             C.POINTER(_d), C.POINTER(_d)]),
+}
+
 _lib = None
 
 
@@ -151,7 +158,7 @@ def load():
             f"{LIB_PATH} not found: build the HIP extension first (python -m microaligner_amd.build). "
             "microaligner_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

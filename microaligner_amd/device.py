@@ -760,6 +760,36 @@ class Context:
         return (np.frombuffer(s0, dtype=np.float64, count=got.value).copy(),
                 np.frombuffer(s1, dtype=np.float64, count=got.value).copy())
 
+    # registration quality maps (include/microaligner_qc.h) ------------------------------------------------------------
+    def qc_nmi_grid(self, ref, b0, b1, cell_h, cell_w):
+        """Per cell of the (cell_h, cell_w) grid: NMI and Pearson r of the u8 labels (ref, b0) and, unless b1 is None,
+        (ref, b1).  -> (nmi0, nmi1, ncc0, ncc1), each (gy, gx) float64 (the b1 pair None without b1)."""
+        for b in (b0, b1):
+            if b is not None and (ref.dtype != np.uint8 or b.dtype != np.uint8 or ref.shape != b.shape or ref.ndim != 2):
+                raise ValueError("QC labels must be 2-D uint8 arrays of equal shape")
+        h, w = ref.shape
+        gy, gx = -(-h // int(cell_h)), -(-w // int(cell_w))
+        pd = C.POINTER(C.c_double)
+        nmi0, ncc0 = np.empty((gy, gx)), np.empty((gy, gx))
+        nmi1, ncc1 = (np.empty((gy, gx)), np.empty((gy, gx))) if b1 is not None else (None, None)
+        self._run(self.lib.ma_qc_nmi_grid, ref.ptr, b0.ptr, b1.ptr if b1 is not None else None, h, w, int(cell_h), int(cell_w),
+                  nmi0.ctypes.data_as(pd), nmi1.ctypes.data_as(pd) if nmi1 is not None else None, ncc0.ctypes.data_as(pd),
+                  ncc1.ctypes.data_as(pd) if ncc1 is not None else None)
+        return nmi0, nmi1, ncc0, ncc1
+
+    def qc_flow_grid(self, flow, cell_h, cell_w):
+        """Per cell of an (h, w, 2) float32 flow: (jac_min, folded, invalid, flow_mean, flow_max), each (gy, gx)."""
+        if flow.dtype != np.float32 or flow.ndim != 3 or flow.shape[2] != 2:
+            raise ValueError(f"flow must be float32 of shape (H, W, 2), got {flow.dtype} {flow.shape}")
+        h, w = flow.shape[:2]
+        gy, gx = -(-h // int(cell_h)), -(-w // int(cell_w))
+        pd, pl = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+        jmin, mean, mx = np.empty((gy, gx)), np.empty((gy, gx)), np.empty((gy, gx))
+        folded, invalid = np.empty((gy, gx), np.int64), np.empty((gy, gx), np.int64)
+        self._run(self.lib.ma_qc_flow_grid, flow.ptr, h, w, int(cell_h), int(cell_w), jmin.ctypes.data_as(pd),
+                  folded.ctypes.data_as(pl), invalid.ctypes.data_as(pl), mean.ctypes.data_as(pd), mx.ctypes.data_as(pd))
+        return jmin, folded, invalid, mean, mx
+
     def max_project(self, stack):
         nz = stack.shape[0]
         out = self.empty(stack.shape[1:], stack.dtype)
