@@ -74,16 +74,16 @@ struct DogScalars {
     float a, b;        // normalize(src, 0, 1, MINMAX, 32F):  v*a + b
     float a8, b8;      // normalize(diff, 0, 255, MINMAX, 8U): v*a8 + b8
     int src_max_is_zero;
+    int src_nan;       // the input holds a NaN (numpy's max() is then NaN): looked for only when mm_src[1] == 0
 };
 
-// normalize(src, 0, 1, NORM_MINMAX, CV_32F): scale rounded to float, shift = (float)0 - (float)(smin*scale)
-// sticky (may be NULL): set to 1 when the input's maximum is exactly 0 but the image is not all zero -- the one input
-// for which the reference's dog() returns the image UNCHANGED (optflow_registrator.py:256-257) and the uint8 result
-// of this chain is not what it goes on with; ma_optflow_register reports it (register.hip)
-__device__ __forceinline__ void d_dog_params_in(DogScalars* s, float mn, float mx, int* sticky)
+// normalize(src, 0, 1, NORM_MINMAX, CV_32F): scale rounded to float, shift = (float)0 - (float)(smin*scale).
+// (mn, mx) ignore NaN (minMaxIdx); src_max_is_zero is provisional until dog_nan_scan has looked for NaN
+// (d_dog_params_out)
+__device__ __forceinline__ void d_dog_params_in(DogScalars* s, float mn, float mx)
 {
-    if (sticky && mx == 0.f && mn < 0.f) atomicOr(sticky, 1);
     s->mm_src[0] = mn; s->mm_src[1] = mx;
+    s->src_nan = 0;
     double smin = mn, smax = mx;
     double scale = (1.0 - 0.0) * (smax - smin > DBL_EPSILON ? 1. / (smax - smin) : 0);
     scale = (float)scale;
@@ -91,9 +91,15 @@ __device__ __forceinline__ void d_dog_params_in(DogScalars* s, float mn, float m
     s->b = (float)0.0 - (float)(smin * scale);
     s->src_max_is_zero = smax == 0.0;
 }
-// normalize(diff, 0, 255, NORM_MINMAX, CV_8U): scale/shift in double, applied in float
-__device__ __forceinline__ void d_dog_params_out(DogScalars* s, float mn, float mx)
+// normalize(diff, 0, 255, NORM_MINMAX, CV_8U): scale/shift in double, applied in float.
+// The reference's zero test is numpy's img.max() == 0 (optflow_registrator.py:256), which a NaN makes false.
+// sticky (may be NULL): set to 1 when that test holds but the image is not all zero -- the one input for which the
+// reference's dog() returns the image UNCHANGED (optflow_registrator.py:256-257) and the uint8 result of this chain is
+// not what it goes on with; ma_optflow_register reports it (register.hip)
+__device__ __forceinline__ void d_dog_params_out(DogScalars* s, float mn, float mx, int* sticky)
 {
+    s->src_max_is_zero = s->src_max_is_zero && !s->src_nan;
+    if (sticky && s->src_max_is_zero && s->mm_src[0] < 0.f) atomicOr(sticky, 1);
     s->mm_diff[0] = mn; s->mm_diff[1] = mx;
     double dmin = mn, dmax = mx;
     double scale = 255. * (dmax - dmin > DBL_EPSILON ? 1. / (dmax - dmin) : 0);
@@ -102,19 +108,31 @@ __device__ __forceinline__ void d_dog_params_out(DogScalars* s, float mn, float 
     s->b8 = (float)shift;
 }
 // the input's (min, max) came from the kernel that produced it
-__global__ void dog_params_in(DogScalars* s, const float* __restrict__ mm, int* sticky)
+__global__ void dog_params_in(DogScalars* s, const float* __restrict__ mm)
 {
-    d_dog_params_in(s, mm[0], mm[1], sticky);
+    d_dog_params_in(s, mm[0], mm[1]);
+}
+
+// numpy's img.max() == 0 is false for an image that holds a NaN.  Float sources only, and only when the NaN-ignoring
+// maximum is exactly 0 is the image scanned; otherwise every block returns at once.
+__global__ __launch_bounds__(256) void dog_nan_scan(const float* __restrict__ src, size_t n, DogScalars* sc)
+{
+    if (!sc->src_max_is_zero) return;
+    bool nan = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) nan |= src[i] != src[i];
+    if (nan) atomicOr(&sc->src_nan, 1);
 }
 
 // one block of 1024 threads folds all partial (min, max) pairs; 4 independent 8-byte loads per lane and step
 constexpr int MMF_T = 1024;
 // sc / what: the DOG scalars that follow from this (min, max) are computed by the same thread (what = 1: the input's
 // normalisation, 2: the difference image's) instead of by a kernel of their own
+// The fold starts from (FLT_MAX, -FLT_MAX) as minMaxIdx's does: fminf / fmaxf never take NaN, +-Inf count as values, an
+// all-NaN input gives (FLT_MAX, -FLT_MAX) (the partials start from +-INFINITY, which this seed absorbs).
 __global__ __launch_bounds__(MMF_T) void minmax_final(const float* __restrict__ part, int nparts, float* __restrict__ out,
                                                       DogScalars* __restrict__ sc, int what, int* sticky = nullptr)
 {
-    float lo = INFINITY, hi = -INFINITY;
+    float lo = FLT_MAX, hi = -FLT_MAX;
     const float2* p2 = reinterpret_cast<const float2*>(part);
     for (int i0 = threadIdx.x; i0 < nparts; i0 += 4 * MMF_T) {
         float2 v[4];
@@ -133,15 +151,15 @@ __global__ __launch_bounds__(MMF_T) void minmax_final(const float* __restrict__ 
     if (threadIdx.x == 0) {
         for (int k = 1; k < MMF_T / 64; k++) { lo = fminf(lo, slo[k]); hi = fmaxf(hi, shi[k]); }
         if (out) { out[0] = lo; out[1] = hi; }
-        if (what == 1) d_dog_params_in(sc, lo, hi, sticky);
-        else if (what == 2) d_dog_params_out(sc, lo, hi);
+        if (what == 1) d_dog_params_in(sc, lo, hi);
+        else if (what == 2) d_dog_params_out(sc, lo, hi, sticky);
     }
 }
 
 constexpr int MM_BLOCKS = 2048;
 
 int launch_minmax(ma_ctx* ctx, const void* src, int dtype, size_t n, float* part, float* out2, DogScalars* sc = nullptr,
-                  int what = 0, int* sticky = nullptr)
+                  int what = 0)
 {
     int blocks = (int)((n + 256 * 8 - 1) / (256 * 8));
     if (blocks > MM_BLOCKS) blocks = MM_BLOCKS;
@@ -149,7 +167,7 @@ int launch_minmax(ma_ctx* ctx, const void* src, int dtype, size_t n, float* part
     if (dtype == MA_U8) hipLaunchKernelGGL((minmax_partial<uint8_t>), dim3(blocks), dim3(256), 0, ctx->stream, (const uint8_t*)src, n, part);
     else if (dtype == MA_U16) hipLaunchKernelGGL((minmax_partial<uint16_t>), dim3(blocks), dim3(256), 0, ctx->stream, (const uint16_t*)src, n, part);
     else hipLaunchKernelGGL((minmax_partial<float>), dim3(blocks), dim3(256), 0, ctx->stream, (const float*)src, n, part);
-    hipLaunchKernelGGL(minmax_final, dim3(1), dim3(MMF_T), 0, ctx->stream, part, blocks, out2, sc, what, sticky);
+    hipLaunchKernelGGL(minmax_final, dim3(1), dim3(MMF_T), 0, ctx->stream, part, blocks, out2, sc, what, (int*)nullptr);
     MA_HIP(hipGetLastError());
     return MA_OK;
 }
@@ -490,7 +508,8 @@ __global__ __launch_bounds__(256) void max_project_kernel(const T* __restrict__ 
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         T m = planes[i];
-        for (int z = 1; z < nz; z++) { T v = planes[(size_t)z * n + i]; m = v > m ? v : m; }
+        // m = np.maximum(m, v): a NaN in any plane wins, a tie (+0 / -0) gives v; m != m is false for integer T
+        for (int z = 1; z < nz; z++) { T v = planes[(size_t)z * n + i]; m = (m > v || m != m) ? m : v; }
         dst[i] = m;
     }
 }
@@ -639,10 +658,12 @@ static int dog_u8_impl(ma_ctx* ctx, const void* src, int dtype, int h, int w, in
     MaProfScope ps(ctx, MA_K_DOG, (double)n);
     // the scalars of the two normalisations are computed by the last thread of the reduction they follow from
     if (src_minmax_dev) {  // the producer of `src` already reduced it
-        hipLaunchKernelGGL(dog_params_in, dim3(1), dim3(1), 0, ctx->stream, sc, src_minmax_dev, ctx->dog_sticky);
+        hipLaunchKernelGGL(dog_params_in, dim3(1), dim3(1), 0, ctx->stream, sc, src_minmax_dev);
     } else {
-        MA_TRY(launch_minmax(ctx, src, dtype, n, part, nullptr, sc, 1, ctx->dog_sticky));
+        MA_TRY(launch_minmax(ctx, src, dtype, n, part, nullptr, sc, 1));
     }
+    if (dtype == MA_F32)
+        hipLaunchKernelGGL(dog_nan_scan, dim3(std::min(grid_for(n), 256)), dim3(256), 0, ctx->stream, (const float*)src, n, sc);
     if (fused) {
         const dim3 grid(ma_xcd_grid((long long)nblk)), block(64 * DF_NW);
 #define MA_DOG_FUSED(T, SP)                                                                                                  \
@@ -678,7 +699,7 @@ static int dog_u8_impl(ma_ctx* ctx, const void* src, int dtype, int h, int w, in
 #undef MA_DOG_COLS
     }
     hipLaunchKernelGGL(minmax_final, dim3(1), dim3(MMF_T), 0, ctx->stream, part, (int)nblk, (float*)nullptr, sc, 2,
-                       (int*)nullptr);
+                       ctx->dog_sticky);
     hipLaunchKernelGGL((scale_to_u8<float>), dim3(grid_for(n)), dim3(256), 0, ctx->stream, diff, n, 0.f, 0.f, sc, dst, fscale);
     MA_HIP(hipGetLastError());
     if (src_max_is_zero_host && (flags & MA_DOG_REPORT_ASYNC)) {

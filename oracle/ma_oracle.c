@@ -838,12 +838,15 @@ int orc_pyr_up_f32(const float* src, int cn, int h, int w, float* dst, int dh, i
 /* ------------------------------------------------------------------------- */
 /* normalize(NORM_MINMAX) + GaussianBlur: the dog() chain (A.5)               */
 /* ------------------------------------------------------------------------- */
+/* minMaxIdx's scalar path (minmax.cpp): the fold starts from (FLT_MAX, -FLT_MAX) and compares with < / >, so NaN
+ * is never taken, +-Inf are taken as values, and an all-NaN image gives (FLT_MAX, -FLT_MAX).  Integer inputs are
+ * never outside that range: the seed only matters for float. */
 int orc_minmax(const void* src, int dtype, size_t n, double* mn, double* mx)
 {
     if (n == 0) return ORC_EINVAL;
-    double lo = load_as_f32(src, dtype, 0), hi = lo;
+    double lo = FLT_MAX, hi = -FLT_MAX;
 #pragma omp parallel for schedule(static) num_threads(g_row_threads) reduction(min : lo) reduction(max : hi)
-    for (size_t i = 1; i < n; i++) {
+    for (size_t i = 0; i < n; i++) {
         double v = load_as_f32(src, dtype, i);
         if (v < lo) lo = v;
         if (v > hi) hi = v;

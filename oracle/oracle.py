@@ -53,6 +53,8 @@ def lib():
         _lib.orc_pyr_down.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib.orc_pyr_up_f32.restype = C.c_int
         _lib.orc_pyr_up_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        _lib.orc_minmax.restype = C.c_int
+        _lib.orc_minmax.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib.orc_normalize_minmax_to_f32.restype = C.c_int
         _lib.orc_normalize_minmax_to_f32.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_double,
                                                      C.c_void_p]
@@ -207,6 +209,14 @@ def pyr_up(img, dstsize=None):
 # DOG_FUSED_BLUR | DOG_FUSED_SCALE = fused multiply-adds (the AVX2 + FMA3 objects an x86-64 host dispatches to).
 DOG_FUSED_BLUR, DOG_FUSED_SCALE = 1, 2
 DOG_FUSED = DOG_FUSED_BLUR | DOG_FUSED_SCALE
+
+
+def minmax(img):
+    """cv2.minMaxIdx's (min, max) of any u8 / u16 / f32 array: NaN ignored, +-Inf taken, all NaN -> (FLT_MAX, -FLT_MAX)."""
+    img, dt = _img(img)
+    mn, mx = C.c_double(), C.c_double()
+    _check(lib().orc_minmax(_p(img), dt, img.size, C.byref(mn), C.byref(mx)), "minmax")
+    return mn.value, mx.value
 
 
 def normalize_minmax_f32(img, alpha=0.0, beta=1.0, fused=False):

@@ -355,6 +355,18 @@ def test_max_project_and_normalize_u8(ctx):
     got = ctx.normalize_minmax_u8(mp).numpy()
     exp = O.normalize_minmax_u8(stack.max(0).astype(np.float32))
     assert np.array_equal(got, exp)
+    # float32 with NaN in planes >= 1 only: np.maximum (utils.py:92) propagates them, normalize sends them to 0
+    from microaligner_amd import max_project_and_normalize
+    fs = (stack / np.float32(7)).astype(np.float32)
+    fs[1, 0, 0] = np.nan
+    fs[2, 60:70, 10:90] = np.nan
+    fs[4, -1, -1] = np.nan
+    fmp = np.maximum.reduce(fs)
+    got_mp = ctx.max_project(ctx.asdevice(fs)).numpy()
+    assert np.array_equal(np.isnan(got_mp), np.isnan(fmp)) and np.array_equal(got_mp, fmp, equal_nan=True)
+    fexp = O.normalize_minmax_u8(fmp)
+    assert np.array_equal(max_project_and_normalize(fs), fexp)
+    assert not fexp[0, 0] and not fexp[-1, -1] and fexp.any()
 
 
 # ---- NMI ------------------------------------------------------------------------------------------------------
