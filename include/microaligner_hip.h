@@ -179,7 +179,10 @@ int ma_event_elapsed_ms(ma_ctx* ctx, void* ev_start, void* ev_stop, float* ms); 
  * launch count per kernel id (enum ma_kernel_id). */
 enum ma_kernel_id {
     MA_K_POLYEXP_M0 = 0, MA_K_BLUR_V = 1, MA_K_BLUR_H_SOLVE = 2, MA_K_WARP = 3, MA_K_MERGE = 4,
-    MA_K_PYR_DOWN = 5, MA_K_PYR_UP = 6, MA_K_DOG = 7, MA_K_NMI = 8, MA_K_OTHER = 9, MA_K_COUNT = 10
+    MA_K_PYR_DOWN = 5, MA_K_PYR_UP = 6, MA_K_DOG = 7, MA_K_NMI = 8, MA_K_OTHER = 9,
+    /* pyramid levels of ma_farneback_levels (its iterations count as MA_K_BLUR_V / MA_K_BLUR_H_SOLVE) */
+    MA_K_FB_LEVEL_IMG = 10, MA_K_FB_POLYEXP_PLAIN = 11, MA_K_FB_FLOW_RESIZE = 12, MA_K_FB_UPDATE_MATRICES = 13,
+    MA_K_COUNT = 14
 };
 int ma_profile_enable(ma_ctx* ctx, int on);
 int ma_profile_reset(ma_ctx* ctx);
@@ -204,6 +207,13 @@ int ma_profile_get(ma_ctx* ctx, int kernel_id, double* total_ms, long long* laun
 int ma_farneback_tiled(ma_ctx* ctx, const void* prev, const void* next, int dtype, int H, int W,
                        int tile, int overlap, int winsize, int iterations, int poly_n,
                        double poly_sigma, int flags, float* flow_out);
+
+/* cv2.calcOpticalFlowFarneback(prev, next, None, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma,
+ * OPTFLOW_FARNEBACK_GAUSSIAN) on the whole image.  levels == 0 is ma_farneback_tiled(tile = 0), bit for bit;
+ * levels beyond OpenCV's 32-px minimum are dropped as OpenCV drops them.  pyr_scale must be 0.5, poly_n 1. */
+int ma_farneback_levels(ma_ctx* ctx, const void* prev, const void* next, int dtype, int H, int W, int levels,
+                        double pyr_scale, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                        float* flow_out);
 
 /* Debug/validation variant for one untiled plane pair: also returns the
  * polynomial expansions (planar, 5 x H x W) and the first matrix field M. */

@@ -20,7 +20,8 @@ MA_OPT_COMPANION_STREAM, MA_OPT_WORKSPACE_LIMIT, MA_OPT_WARP_BAND_BYTES = 1, 2, 
 MA_ENGINE_COMPUTE, MA_ENGINE_H2D, MA_ENGINE_D2H = 0, 1, 2   # enum ma_engine
 
 KERNEL_IDS = {"polyexp_m0": 0, "blur_v": 1, "blur_h_solve": 2, "warp": 3, "merge": 4, "pyr_down": 5,
-              "pyr_up": 6, "dog": 7, "nmi": 8, "other": 9}
+              "pyr_up": 6, "dog": 7, "nmi": 8, "other": 9, "fb_level_img": 10, "fb_polyexp_plain": 11,
+              "fb_flow_resize": 12, "fb_update_matrices": 13}
 
 _vp, _i, _sz, _d, _f = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float
 
@@ -55,6 +56,7 @@ SIGNATURES = {
     "ma_profile_reset": (_i, [_vp]),
     "ma_profile_get": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(C.c_longlong), C.POINTER(_d)]),
     "ma_farneback_tiled": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _vp]),
+    "ma_farneback_levels": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _i, _i, _i, _d, _i, _vp]),
     "ma_farneback_debug": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "ma_remap_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "ma_warp_tiled": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),

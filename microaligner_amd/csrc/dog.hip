@@ -521,9 +521,11 @@ __global__ __launch_bounds__(256) void convert_f32_kernel(const T* __restrict__ 
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = (float)src[i];
 }
 
+} // namespace
+
 // getGaussianKernel(ksize, sigma, CV_32F) as OpenCV 4.x computes it (A.5): taps in double,
 // sum = 2*sum(t)+1, multiplied by 1/sum, rounded to float once.
-void gaussian_kernel(int ksize, double sigma, std::vector<float>& k)
+void ma_gaussian_kernel(int ksize, double sigma, std::vector<float>& k)
 {
     k.resize(ksize);
     double sigmaX = sigma > 0 ? sigma : ksize * 0.15 + 0.35;
@@ -545,6 +547,8 @@ void gaussian_kernel(int ksize, double sigma, std::vector<float>& k)
     }
     k[n2] = (float)mul1;
 }
+
+namespace {
 
 int grid_for(size_t n) { size_t b = (n + 256 * 4 - 1) / (256 * 4); return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
 
@@ -628,8 +632,8 @@ static int dog_u8_impl(ma_ctx* ctx, const void* src, int dtype, int h, int w, in
     MA_REQUIRE(lds_rows <= 160 * 1024 && lds_cols <= 160 * 1024, "low_sigma too large for the LDS-staged DOG kernels");
 
     std::vector<float> klo, khi;
-    gaussian_kernel(ksize, low_sigma, klo);
-    gaussian_kernel(ksize, high_sigma, khi);
+    ma_gaussian_kernel(ksize, low_sigma, klo);
+    ma_gaussian_kernel(ksize, high_sigma, khi);
     const float *dlo = nullptr, *dloc = nullptr, *dhic = nullptr;
     const uint64_t key = ((uint64_t)ksize << 16);
     std::vector<float> klh(2 * (size_t)ksize);  // row pass: (lo, hi) interleaved

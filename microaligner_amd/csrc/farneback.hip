@@ -772,6 +772,214 @@ __global__ void fb_copy_planes(FbGeom g, const float* __restrict__ ws, int pl, f
     out[((size_t)k * g.t.Ph + y) * g.t.Pw + x] = ws[((size_t)pl + k) * g.plane + (size_t)y * g.pitch + x];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Pyramid levels: cv2.calcOpticalFlowFarneback with levels > 0 (FarnebackOpticalFlow::calc, CPU path).  Level k > 0
+// of each image is GaussianBlur(ksize_k, sigma_k) of the full-resolution image (reflect-101) resized INTER_LINEAR to
+// (h_k, w_k), then expanded without a further pre-blur; level 0 is fb_polyexp_m0.  The iterations are the kernels above.
+// ---------------------------------------------------------------------------------------------
+// cv::resize INTER_LINEAR taps along one axis (generic path, float data):  f = (float)((d + 0.5) * scale - 0.5),
+// s = cvFloor(f), f -= s, weights (1 - f, f) in float.  Columns: s < 0 -> s = 0, f = 0; once s + 1 >= ssz (dx >= xmax)
+// the value is S[ssz - 1] alone ("tail").  Rows: the weights are kept and both rows are clamped into [0, ssz).
+struct RsTap { int s0, s1; float a0, a1; bool tail; };
+__device__ __forceinline__ RsTap rs_tap_x(int d, double scale, int ssz)
+{
+    RsTap t;
+    float f = (float)((d + 0.5) * scale - 0.5);
+    int s = d_cvfloor(f);
+    f -= (float)s;
+    if (s < 0) { s = 0; f = 0.f; }
+    t.tail = s + 1 >= ssz;
+    if (t.tail) { s = ssz - 1; f = 0.f; }
+    t.s0 = s; t.s1 = min(s + 1, ssz - 1);
+    t.a0 = 1.f - f; t.a1 = f;
+    return t;
+}
+__device__ __forceinline__ RsTap rs_tap_y(int d, double scale, int ssz)
+{
+    RsTap t;
+    float f = (float)((d + 0.5) * scale - 0.5);
+    const int s = d_cvfloor(f);
+    f -= (float)s;
+    t.s0 = d_clamp(s, 0, ssz - 1); t.s1 = d_clamp(s + 1, 0, ssz - 1);
+    t.a0 = 1.f - f; t.a1 = f;
+    t.tail = false;
+    return t;
+}
+
+// Row pass of a level's GaussianBlur, only at the source columns the resize reads: tmp[y][2 dx + t] is the row-filtered
+// value at column s_t(dx) of rs_tap_x (the 2x2 area case reads columns 2dx, 2dx+1, which the same taps give at scale 2).
+// acc = k0 * x_0; acc += k_j * x_j for j = 1..ksize-1, left to right (orc_gaussian_blur_f32_ex).  The block's source
+// span is staged in LDS in chunks, a thread walks the taps that fall in each chunk in order: any ksize, one kernel.
+constexpr int LV_THREADS = 256, LV_CHUNK = 2048;
+template <typename T, bool FUSED>
+__global__ __launch_bounds__(LV_THREADS) void fb_level_rows(const T* __restrict__ src, int H, int W, int wk, double scale_x,
+                                                            const float* __restrict__ k, int ksize, float* __restrict__ tmp)
+{
+    __shared__ float seg[LV_CHUNK];
+    const int ncol = 2 * wk, r = ksize / 2;
+    const int c0 = blockIdx.x * LV_THREADS, c = c0 + threadIdx.x;
+    auto col_of = [&](int cc) { const RsTap t = rs_tap_x(cc >> 1, scale_x, W); return (cc & 1) ? t.s1 : t.s0; };
+    const int lo = col_of(c0) - r, hi = col_of(min(c0 + LV_THREADS, ncol) - 1) + r;   // col_of is non-decreasing
+    const int sc = c < ncol ? col_of(c) - r : 0;                                          // column of this thread's tap 0
+    for (int y = blockIdx.y; y < H; y += gridDim.y) {
+        const T* row = src + (size_t)y * W;
+        float acc = 0.f;
+        for (int cs = lo; cs <= hi; cs += LV_CHUNK) {
+            const int n = min(LV_CHUNK, hi + 1 - cs);
+            for (int i = threadIdx.x; i < n; i += LV_THREADS) seg[i] = (float)row[d_reflect101(cs + i, W)];
+            __syncthreads();
+            if (c < ncol) {
+                const int j1 = min(ksize, cs + n - sc);
+                for (int j = max(0, cs - sc); j < j1; j++) {
+                    const float v = seg[sc + j - cs];
+                    acc = j == 0 ? __fmul_rn(k[0], v) : d_muladd<FUSED>(k[j], v, acc);
+                }
+            }
+            __syncthreads();
+        }
+        if (c < ncol) tmp[(size_t)y * ncol + c] = acc;
+    }
+}
+
+// Column pass at the rows the resize reads, then the resize itself, into a planar f32 level image (pitch floats per row).
+// Column filter: d = k_r * c; d += k_{r+j} * (row y+j + row y-j), j = 1..r (reflect-101).  Resize: the 2x2 mean
+// ((b00 + b01) + (b10 + b11)) * 0.25 when both inverse scales are exactly 2 (cv::resize's INTER_AREA fast path), else
+// per row h = b0 * a0 + b1 * a1 (or the tail column alone), then muladd(h0, beta0, h1 * beta1).
+template <bool FUSED>
+__global__ __launch_bounds__(256) void fb_level_cols(const float* __restrict__ tmp, int H, int W, int wk, int hk,
+                                                     double scale_x, double scale_y, int area, const float* __restrict__ k,
+                                                     int ksize, float* __restrict__ dst, int pitch)
+{
+    const int dx = blockIdx.x * 256 + threadIdx.x;
+    if (dx >= wk) return;
+    const int ncol = 2 * wk, r = ksize / 2;
+    const float* col = tmp + 2 * dx;
+    auto blur = [&](int y, int t) {
+        float d = __fmul_rn(k[r], col[(size_t)y * ncol + t]);
+        for (int j = 1; j <= r; j++)
+            d = d_muladd<FUSED>(k[r + j], col[(size_t)d_reflect101(y + j, H) * ncol + t] + col[(size_t)d_reflect101(y - j, H) * ncol + t], d);
+        return d;
+    };
+    const RsTap tx = rs_tap_x(dx, scale_x, W);
+    for (int dy = blockIdx.y; dy < hk; dy += gridDim.y) {
+        float out;
+        if (area) {
+            const float b00 = blur(2 * dy, 0), b01 = blur(2 * dy, 1), b10 = blur(2 * dy + 1, 0), b11 = blur(2 * dy + 1, 1);
+            out = ((b00 + b01) + (b10 + b11)) * 0.25f;
+        } else {
+            const RsTap ty = rs_tap_y(dy, scale_y, H);
+            auto hpass = [&](int y) { return tx.tail ? blur(y, 0) : blur(y, 0) * tx.a0 + blur(y, 1) * tx.a1; };
+            const float h0 = hpass(ty.s0), h1 = hpass(ty.s1);
+            out = d_muladd<FUSED>(h0, ty.a0, h1 * ty.a1);
+        }
+        dst[(size_t)dy * pitch + dx] = out;
+    }
+}
+
+// FarnebackPolyExp (poly_n 1, replicate border) of the two level images in the V planes (no pre-blur) -> R0 / R1.
+// Operation by operation steps 4 and 5 of fb_polyexp_m0.
+__global__ __launch_bounds__(256) void fb_polyexp_plain(FbGeom g, PolyConsts pc, float* __restrict__ ws)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, img = blockIdx.z;
+    const int Ph = g.t.Ph, Pw = g.t.Pw;
+    if (x >= Pw) return;
+    const float* src = ws + (size_t)(PL_V + img) * g.plane;
+    float* dst = ws + (size_t)(img == 0 ? PL_R0 : PL_R1) * g.plane;
+    for (int y = blockIdx.y; y < Ph; y += gridDim.y) {
+        const float* up = src + (size_t)max(y - 1, 0) * g.pitch;
+        const float* ce = src + (size_t)y * g.pitch;
+        const float* dn = src + (size_t)min(y + 1, Ph - 1) * g.pitch;
+        float vt[3][3];   // vertical pass at columns x-1, x, x+1 (replicated)
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const int xx = d_clamp(x - 1 + i, 0, Pw - 1);
+            const float u = up[xx], cc = ce[xx], d = dn[xx];
+            const float p = u + d;
+            const float row0 = cc * pc.g0;
+            vt[0][i] = row0 + pc.g1 * p;
+            vt[1][i] = 0.f + pc.xg1 * (d - u);
+            vt[2][i] = 0.f + pc.xxg1 * p;
+        }
+        const float a0m = vt[0][0], a0 = vt[0][1], a0p = vt[0][2];
+        const float a1m = vt[1][0], a1 = vt[1][1], a1p = vt[1][2];
+        const float a2m = vt[2][0], a2 = vt[2][1], a2p = vt[2][2];
+        double b1 = (double)(a0 * pc.g0), b3 = (double)(a1 * pc.g0), b5 = (double)(a2 * pc.g0);
+        const double tg = (double)(a0p + a0m);
+        b1 += tg * (double)pc.g1;
+        const double b4 = 0.0 + tg * (double)pc.xxg1;
+        const double b2 = 0.0 + (double)((a0p - a0m) * pc.xg1);
+        b3 += (double)((a1p + a1m) * pc.g1);
+        const double b6 = 0.0 + (double)((a1p - a1m) * pc.xg1);
+        b5 += (double)((a2p + a2m) * pc.g1);
+        const size_t pix = (size_t)y * g.pitch + x;
+        dst[1 * g.plane + pix] = (float)(b2 * pc.ig11);
+        dst[0 * g.plane + pix] = (float)(b3 * pc.ig11);
+        dst[3 * g.plane + pix] = (float)(b1 * pc.ig03 + b4 * pc.ig33);
+        dst[2 * g.plane + pix] = (float)(b1 * pc.ig03 + b5 * pc.ig33);
+        dst[4 * g.plane + pix] = (float)(b6 * pc.ig55);
+    }
+}
+
+// Initial flow of a level: resize(flow of level k+1, (dw, dh), INTER_LINEAR) * (1 / pyr_scale), interleaved (dx, dy).
+// The vertical step is muladd(h0, beta0, h1 * beta1) as for the level images; x * 2 + 0 is convertTo's scale.
+template <bool FUSED>
+__global__ __launch_bounds__(256) void fb_flow_resize(const float* __restrict__ src, int sw, int sh, double scale_x,
+                                                      double scale_y, float* __restrict__ dst, int dw, int dh)
+{
+    const int dx = blockIdx.x * 256 + threadIdx.x;
+    if (dx >= dw) return;
+    const RsTap tx = rs_tap_x(dx, scale_x, sw);
+    for (int dy = blockIdx.y; dy < dh; dy += gridDim.y) {
+        const RsTap ty = rs_tap_y(dy, scale_y, sh);
+        const float* r0 = src + (size_t)ty.s0 * sw * 2;
+        const float* r1 = src + (size_t)ty.s1 * sw * 2;
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            const float h0 = tx.tail ? r0[tx.s0 * 2 + c] : r0[tx.s0 * 2 + c] * tx.a0 + r0[tx.s1 * 2 + c] * tx.a1;
+            const float h1 = tx.tail ? r1[tx.s0 * 2 + c] : r1[tx.s0 * 2 + c] * tx.a0 + r1[tx.s1 * 2 + c] * tx.a1;
+            const float v = d_muladd<FUSED>(h0, ty.a0, h1 * ty.a1);
+            dst[((size_t)dy * dw + dx) * 2 + c] = v * 2.f + 0.f;
+        }
+    }
+}
+
+// FarnebackUpdateMatrices(R0, R1, flow) over a whole level (A.1 step 3) -> M: the epilogue of fb_blur_h_solve_simple
+// with the flow read from an interleaved (h, w, 2) buffer.
+__global__ __launch_bounds__(256) void fb_update_matrices(FbGeom g, const float* __restrict__ flow, float* __restrict__ ws)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int Ph = g.t.Ph, Pw = g.t.Pw;
+    if (x >= Pw) return;
+    const float* R0p = ws + (size_t)PL_R0 * g.plane;
+    const float* R1p = ws + (size_t)PL_R1 * g.plane;
+    float* Mp = ws + (size_t)PL_M * g.plane;
+    for (int y = blockIdx.y; y < Ph; y += gridDim.y) {
+        const size_t pix = (size_t)y * g.pitch + x;
+        const float dx = flow[((size_t)y * Pw + x) * 2], dy = flow[((size_t)y * Pw + x) * 2 + 1];
+        float r0[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) r0[k] = R0p[k * g.plane + pix];
+        float fx = (float)x + dx, fy = (float)y + dy;
+        const int x1 = d_cvfloor(fx), y1 = d_cvfloor(fy);
+        fx -= (float)x1; fy -= (float)y1;
+        float r[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        const bool inside = (unsigned)x1 < (unsigned)(Pw - 1) && (unsigned)y1 < (unsigned)(Ph - 1);
+        if (inside) {
+            const float a00 = (1.f - fx) * (1.f - fy), a01 = fx * (1.f - fy), a10 = (1.f - fx) * fy, a11 = fx * fy;
+            const float* q = R1p + (size_t)y1 * g.pitch + x1;
+#pragma unroll
+            for (int k = 0; k < 5; k++) {
+                const float* qk = q + k * g.plane;
+                r[k] = a00 * qk[0] + a01 * qk[1] + a10 * qk[g.pitch] + a11 * qk[g.pitch + 1];
+            }
+        }
+        float Mv[5];
+        update_matrices_px(r0, r[0], r[1], r[2], r[3], r[4], inside, dx, dy, x, y, Pw, Ph, Mv);
+#pragma unroll
+        for (int k = 0; k < 5; k++) Mp[k * g.plane + pix] = Mv[k];
+    }
+}
+
 // ---- host side ------------------------------------------------------------------------------
 
 // hal::Cholesky64f-style SPD solve, as used by Mat::inv(DECOMP_CHOLESKY) (A.1 step 2)
@@ -872,48 +1080,67 @@ constexpr int BH_R = 14, BH_NW = 8 * BH_ROWS / 64;
 constexpr int BH_TXW = BH_NW * BH_R * (64 / BH_ROWS);
 constexpr size_t LDS_MAX = 160 * 1024;
 
-template <typename T, bool FUSED>
-int run_batch(ma_ctx* ctx, const T* prev, const T* next, FbGeom g, int nwin, const PolyConsts& pc, int m,
-              const float* taps, int iters, float* flow_out)
+// What the iterations of one batch process: whether the LDS-staged kernels serve the window size, and the pixels of
+// every launch (the unit of the per-kernel accounting).  Sets g.margin, which the expansion kernel reads too.
+struct FbPlan {
+    bool fast;
+    double px;                        // active extent: the expansion kernel and the fallback passes
+    std::vector<double> px_v, px_h;   // active extent x needed rectangle, per iteration
+};
+
+FbPlan plan_batch(FbGeom& g, int nwin, int m, int iters)
 {
-    float* ws = (float*)ctx->ws;
+    FbPlan p;
     const int Ph = g.t.Ph, Pw = g.t.Pw;
     const size_t lds_v = (size_t)(BV_NW * BV_R + 2 * m + 4) * 64 * sizeof(float);
     const int colsh = BH_TXW + 2 * m + 4;
     size_t lds_h = (size_t)BH_ROWS * (colsh | 1) * sizeof(float);
     const size_t lds_t = (size_t)BH_ROWS * (BH_TXW + 1) * 2 * sizeof(float);   // the flow on its way to the x-major epilogue
     if (lds_t > lds_h) lds_h = lds_t;
-    const bool fast = m >= 1 && lds_v <= LDS_MAX && lds_h <= LDS_MAX && colsh <= 320;  // 320 = 5 chunks (winsize <= 253)
+    p.fast = m >= 1 && lds_v <= LDS_MAX && lds_h <= LDS_MAX && colsh <= 320;  // 320 = 5 chunks (winsize <= 253)
     // the LDS-staged kernels honour the active extent; the fallback kernels process whole windows
-    g.margin = fast ? (iters - 1) * m + 3 : (1 << 28);
+    g.margin = p.fast ? (iters - 1) * m + 3 : (1 << 28);
     // pixels actually processed -- the unit of the per-kernel accounting: the active extent for the expansion
     // kernel, active extent x needed rectangle for the two passes of every iteration
-    double px = 0;
-    std::vector<double> px_v(iters, 0.0), px_h(iters, 0.0);
+    p.px = 0;
+    p.px_v.assign(iters, 0.0);
+    p.px_h.assign(iters, 0.0);
     for (int wl = 0; wl < nwin; wl++) {
         int oy = 0, ox = 0;
         if (g.t.T > 0) { int ty = (g.tile0 + wl) / g.t.ntx, tx = (g.tile0 + wl) % g.t.ntx; oy = ty * g.t.T - g.t.ov; ox = tx * g.t.T - g.t.ov; }
         const int vy = std::min(Ph, g.t.H - oy), vx = std::min(Pw, g.t.W - ox);
         const int ey = std::min(Ph, vy + std::min(g.margin, Ph)), ex = std::min(Pw, vx + std::min(g.margin, Pw));
-        px += (double)ey * ex;
+        p.px += (double)ey * ex;
         for (int it = 0; it < iters; it++) {
-            const int reach = fast ? (iters - 1 - it) * m : (1 << 28) / 2;
+            const int reach = p.fast ? (iters - 1 - it) * m : (1 << 28) / 2;
             const FbRect rh = needed_rect_h(g.t, oy, ox, reach), rv = needed_rect_v(g.t, oy, ox, reach, m);
-            px_h[it] += (double)std::max(0, std::min(ey, rh.y1) - rh.y0) * std::max(0, std::min(ex, rh.x1) - rh.x0);
-            px_v[it] += (double)std::max(0, std::min(ey, rv.y1) - rv.y0) * std::max(0, std::min(ex, rv.x1) - rv.x0);
+            p.px_h[it] += (double)std::max(0, std::min(ey, rh.y1) - rh.y0) * std::max(0, std::min(ex, rh.x1) - rh.x0);
+            p.px_v[it] += (double)std::max(0, std::min(ey, rv.y1) - rv.y0) * std::max(0, std::min(ex, rv.x1) - rv.x0);
         }
     }
-    {
-        MaProfScope ps(ctx, MA_K_POLYEXP_M0, px);
-        dim3 grid((Pw + K1_TX - 1) / K1_TX, (Ph + K1_TY - 1) / K1_TY, nwin);
-        hipLaunchKernelGGL((fb_polyexp_m0<T>), grid, dim3(K1_THREADS), 0, ctx->stream, prev, next, g, pc, ws);
-    }
+    return p;
+}
+
+// The `iters` window-blur + solve iterations on the M planes of a batch (A.1 step 4), the last one writing the flow.
+// Shared by the tiled path (run_batch) and every level of the pyramid (run_levels).
+template <bool FUSED>
+void run_iterations(ma_ctx* ctx, const FbGeom& g, const FbPlan& p, int nwin, int m, const float* taps, int iters,
+                    float* flow_out)
+{
+    float* ws = (float*)ctx->ws;
+    const int Ph = g.t.Ph, Pw = g.t.Pw;
+    const size_t lds_v = (size_t)(BV_NW * BV_R + 2 * m + 4) * 64 * sizeof(float);
+    const int colsh = BH_TXW + 2 * m + 4;
+    size_t lds_h = (size_t)BH_ROWS * (colsh | 1) * sizeof(float);
+    const size_t lds_t = (size_t)BH_ROWS * (BH_TXW + 1) * 2 * sizeof(float);
+    if (lds_t > lds_h) lds_h = lds_t;
+    const bool fast = p.fast;
     for (int it = 0; it < iters; it++) {
         const int last = it == iters - 1;
         const int reach = (iters - 1 - it) * m;  // see needed_rect_h
         if (fast) {
             {
-                MaProfScope ps(ctx, MA_K_BLUR_V, px_v[it]);
+                MaProfScope ps(ctx, MA_K_BLUR_V, p.px_v[it]);
                 // the streaming form needs whole tap groups (m % (R/2) == 0: the reference's window of 99) and its ring in LDS
                 const size_t lds_vs = (size_t)(BVS_NW * BV_R + 2 * m + 4 + 3 * (BV_R / 2) + 1) * 64 * sizeof(float);
                 if (m % (BV_R / 2) == 0 && lds_vs <= LDS_MAX) {
@@ -927,7 +1154,7 @@ int run_batch(ma_ctx* ctx, const T* prev, const T* next, FbGeom g, int nwin, con
                 }
             }
             {
-                MaProfScope ps(ctx, MA_K_BLUR_H_SOLVE, px_h[it]);
+                MaProfScope ps(ctx, MA_K_BLUR_H_SOLVE, p.px_h[it]);
                 const long long items = (long long)((Pw + BH_TXW - 1) / BH_TXW) * ((Ph + BH_ROWS - 1) / BH_ROWS) * ma_xcd_slots(nwin);
                 // Q = 64-column chunks of the staged row tile (112 + 2m + 4 columns)
 #define MA_BLUR_H(QQ)                                                                                               \
@@ -944,18 +1171,32 @@ int run_batch(ma_ctx* ctx, const T* prev, const T* next, FbGeom g, int nwin, con
             }
         } else {
             {
-                MaProfScope ps(ctx, MA_K_BLUR_V, px);
+                MaProfScope ps(ctx, MA_K_BLUR_V, p.px);
                 dim3 grid((Pw + 255) / 256, Ph, nwin * 5);
                 hipLaunchKernelGGL((fb_blur_v_simple<FUSED>), grid, dim3(256), 0, ctx->stream, g, m, taps, ws);
             }
             {
-                MaProfScope ps(ctx, MA_K_BLUR_H_SOLVE, px);
+                MaProfScope ps(ctx, MA_K_BLUR_H_SOLVE, p.px);
                 dim3 grid((Pw + 255) / 256, Ph, nwin);
                 hipLaunchKernelGGL((fb_blur_h_solve_simple<FUSED>), grid, dim3(256), 0, ctx->stream, g, m, taps, ws,
                                    last, flow_out);
             }
         }
     }
+}
+
+template <typename T, bool FUSED>
+int run_batch(ma_ctx* ctx, const T* prev, const T* next, FbGeom g, int nwin, const PolyConsts& pc, int m,
+              const float* taps, int iters, float* flow_out)
+{
+    float* ws = (float*)ctx->ws;
+    const FbPlan p = plan_batch(g, nwin, m, iters);
+    {
+        MaProfScope ps(ctx, MA_K_POLYEXP_M0, p.px);
+        dim3 grid((g.t.Pw + K1_TX - 1) / K1_TX, (g.t.Ph + K1_TY - 1) / K1_TY, nwin);
+        hipLaunchKernelGGL((fb_polyexp_m0<T>), grid, dim3(K1_THREADS), 0, ctx->stream, prev, next, g, pc, ws);
+    }
+    run_iterations<FUSED>(ctx, g, p, nwin, m, taps, iters, flow_out);
     MA_HIP(hipGetLastError());
     return MA_OK;
 }
@@ -1026,6 +1267,166 @@ int farneback_impl(ma_ctx* ctx, const void* prev, const void* next, int dtype, i
     return MA_OK;
 }
 
+// One level of OpenCV's pyramid: scale = pyr_scale^k by repeated multiplication in double,
+// sigma = (1/scale - 1) / 2, ksize = max(cvRound(5 sigma) | 1, 3), size = cvRound of the scaled size.
+struct FbLevel { int w, h, ksize; double sigma; };
+
+// OpenCV's level count: levels stop before the first whose scaled width or height is below 32 (dropped, not an error)
+std::vector<FbLevel> level_table(int H, int W, int levels)
+{
+    const double pyr_scale = 0.5;
+    int k;
+    double scale = 1;
+    for (k = 0; k < levels; k++) {
+        scale *= pyr_scale;
+        if (W * scale < 32 || H * scale < 32) break;
+    }
+    std::vector<FbLevel> L(k + 1);
+    for (int i = 0; i <= k; i++) {
+        double s = 1;
+        for (int j = 0; j < i; j++) s *= pyr_scale;
+        const double sigma = (1. / s - 1) * 0.5;
+        L[i].sigma = sigma;
+        L[i].ksize = std::max((int)std::lrint(sigma * 5) | 1, 3);
+        L[i].w = (int)std::lrint(W * s);
+        L[i].h = (int)std::lrint(H * s);
+    }
+    return L;
+}
+
+FbGeom level_geom(const FbLevel& l)
+{
+    FbGeom g;
+    g.t = ma_make_tiling(l.h, l.w, 0, 0);
+    g.pitch = (int)ma_align_up((size_t)l.w, 64);
+    g.plane = (size_t)l.h * g.pitch;
+    g.tile0 = 0;
+    g.margin = 1 << 28;
+    return g;
+}
+
+// cv::resize's inverse scale along one axis: 1 / (dsize / ssize), as resize() forms it
+double rs_scale(int dsz, int ssz) { return 1. / ((double)dsz / ssz); }
+
+// Workspace of the level loop, in floats:  [0, 20 plane_k)  the level's planes (R0, R1, M, V; the level images live in
+// V until the iterations start) | [20 plane_k, +H * 2 w_k)  row pass of the level images (k > 0) | at `flow_off`, the
+// flow of the level just solved (h_1 x w_1 x 2 at most).  The initial flow of each level is built in flow_out.
+struct FbLevelWs { size_t flow_off, total; };
+FbLevelWs level_workspace(const std::vector<FbLevel>& L, int H)
+{
+    FbLevelWs r{0, 0};
+    for (size_t k = 0; k < L.size(); k++) {
+        const FbGeom g = level_geom(L[k]);
+        size_t need = g.plane * PL_COUNT;
+        if (k > 0) need += (size_t)H * 2 * L[k].w;
+        r.flow_off = std::max(r.flow_off, need);
+    }
+    r.total = r.flow_off + (L.size() > 1 ? (size_t)L[1].h * L[1].w * 2 : 0);
+    return r;
+}
+
+template <typename T, bool FUSED>
+int run_levels(ma_ctx* ctx, const T* prev, const T* next, int H, int W, const std::vector<FbLevel>& L, size_t flow_off,
+               const PolyConsts& pc, int m, const float* taps, int iters, float* flow_out)
+{
+    float* ws = (float*)ctx->ws;
+    float* flow_lv = ws + flow_off;
+    const int top = (int)L.size() - 1;
+    for (int k = top; k >= 0; k--) {
+        const FbLevel& l = L[k];
+        FbGeom g = level_geom(l);
+        const FbPlan p = plan_batch(g, 1, m, iters);
+        const double px = (double)l.w * l.h;
+        const unsigned gy = (unsigned)std::min(l.h, MA_GRID_Y_MAX);
+        if (k == 0) {
+            MaProfScope ps(ctx, MA_K_POLYEXP_M0, p.px);
+            dim3 grid((l.w + K1_TX - 1) / K1_TX, (l.h + K1_TY - 1) / K1_TY, 1);
+            hipLaunchKernelGGL((fb_polyexp_m0<T>), grid, dim3(K1_THREADS), 0, ctx->stream, prev, next, g, pc, ws);
+        } else {
+            std::vector<float> kt;
+            ma_gaussian_kernel(l.ksize, l.sigma, kt);
+            const float* dk = nullptr;
+            MA_TRY(ma_const_table(ctx, ((uint64_t)4 << 56) | (uint64_t)k, kt.data(), kt.size(), &dk));
+            // INTER_AREA fast path of cv::resize: both inverse scales exactly 2
+            const int area = W == 2 * l.w && H == 2 * l.h;
+            const double sx = rs_scale(l.w, W), sy = rs_scale(l.h, H);
+            float* tmp = ws + g.plane * PL_COUNT;
+            {
+                MaProfScope ps(ctx, MA_K_FB_LEVEL_IMG, 2 * px);
+                for (int img = 0; img < 2; img++) {
+                    hipLaunchKernelGGL((fb_level_rows<T, FUSED>), dim3((2 * l.w + LV_THREADS - 1) / LV_THREADS,
+                                       (unsigned)std::min(H, MA_GRID_Y_MAX)), dim3(LV_THREADS), 0, ctx->stream,
+                                       img == 0 ? prev : next, H, W, l.w, sx, dk, l.ksize, tmp);
+                    hipLaunchKernelGGL((fb_level_cols<FUSED>), dim3((l.w + 255) / 256, gy), dim3(256), 0, ctx->stream, tmp, H,
+                                       W, l.w, l.h, sx, sy, area, dk, l.ksize, ws + (PL_V + img) * g.plane, g.pitch);
+                }
+            }
+            MaProfScope ps(ctx, MA_K_FB_POLYEXP_PLAIN, 2 * px);
+            hipLaunchKernelGGL(fb_polyexp_plain, dim3((l.w + 255) / 256, gy, 2), dim3(256), 0, ctx->stream, g, pc, ws);
+        }
+        if (k == top) {
+            MA_HIP(hipMemsetAsync(flow_out, 0, (size_t)l.w * l.h * 2 * sizeof(float), ctx->stream));
+        } else {
+            const FbLevel& c = L[k + 1];
+            MaProfScope ps(ctx, MA_K_FB_FLOW_RESIZE, px);
+            hipLaunchKernelGGL((fb_flow_resize<FUSED>), dim3((l.w + 255) / 256, gy), dim3(256), 0, ctx->stream, flow_lv,
+                               c.w, c.h, rs_scale(l.w, c.w), rs_scale(l.h, c.h), flow_out, l.w, l.h);
+        }
+        {
+            MaProfScope ps(ctx, MA_K_FB_UPDATE_MATRICES, px);
+            hipLaunchKernelGGL(fb_update_matrices, dim3((l.w + 255) / 256, gy), dim3(256), 0, ctx->stream, g, flow_out, ws);
+        }
+        run_iterations<FUSED>(ctx, g, p, 1, m, taps, iters, k == 0 ? flow_out : flow_lv);
+        MA_HIP(hipGetLastError());
+    }
+    return MA_OK;
+}
+
+int farneback_levels_impl(ma_ctx* ctx, const void* prev, const void* next, int dtype, int H, int W, int levels,
+                          double pyr_scale, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                          float* flow_out)
+{
+    MA_REQUIRE(levels >= 0, "levels must be >= 0");
+    MA_REQUIRE(pyr_scale == 0.5, "only pyr_scale == 0.5 is supported");
+    if (levels == 0)
+        return farneback_impl(ctx, prev, next, dtype, H, W, 0, 0, winsize, iterations, poly_n, poly_sigma, flags, flow_out,
+                              nullptr, nullptr, nullptr);
+    MA_REQUIRE(ctx && prev && next && flow_out, "NULL argument");
+    MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
+    MA_REQUIRE(H > 0 && W > 0, "image must be non-empty");
+    MA_REQUIRE(winsize >= 1, "winsize must be >= 1");
+    MA_REQUIRE(iterations >= 1, "iterations must be >= 1");
+    MA_REQUIRE(poly_n == 1, "only poly_n == 1 is supported (the value microaligner passes)");
+    const std::vector<FbLevel> L = level_table(H, W, levels);
+    if (L.size() == 1)
+        return farneback_impl(ctx, prev, next, dtype, H, W, 0, 0, winsize, iterations, poly_n, poly_sigma, flags, flow_out,
+                              nullptr, nullptr, nullptr);
+    // the iteration kernels address a window's 20 planes with 32-bit byte offsets
+    MA_REQUIRE(level_geom(L[0]).plane * PL_COUNT * sizeof(float) <= (size_t)INT32_MAX,
+               "image too large for whole-image Farneback (20 planes of the finest level must stay below 2 GiB)");
+    const FbLevelWs lw = level_workspace(L, H);
+    MA_REQUIRE(lw.total * sizeof(float) <= ctx->ws_limit, "the finest level does not fit the workspace limit");
+    MA_HIP(hipSetDevice(ctx->device));
+
+    PolyConsts pc;
+    if (!make_poly_consts(poly_sigma, &pc)) { ma_set_error("polynomial-expansion Gram matrix is singular"); return MA_EINVAL; }
+    const float* taps = nullptr;
+    MA_TRY(get_taps(ctx, winsize, &taps));
+    // reserved once for the whole loop: growing the workspace between levels would free it, which waits for the device
+    MA_TRY(ma_ws_reserve(ctx, lw.total * sizeof(float)));
+    const bool fused = (flags & MA_FB_MULADD_FUSED) != 0;
+    const int m = winsize / 2;
+#define RUN(TYPE)                                                                                                      \
+    (fused ? run_levels<TYPE, true>(ctx, (const TYPE*)prev, (const TYPE*)next, H, W, L, lw.flow_off, pc, m, taps,      \
+                                    iterations, flow_out)                                                              \
+           : run_levels<TYPE, false>(ctx, (const TYPE*)prev, (const TYPE*)next, H, W, L, lw.flow_off, pc, m, taps,     \
+                                     iterations, flow_out))
+    if (dtype == MA_U8) return RUN(uint8_t);
+    if (dtype == MA_U16) return RUN(uint16_t);
+    return RUN(float);
+#undef RUN
+}
+
 } // namespace
 
 extern "C" {
@@ -1036,6 +1437,14 @@ int ma_farneback_tiled(ma_ctx* ctx, const void* prev, const void* next, int dtyp
 {
     return farneback_impl(ctx, prev, next, dtype, H, W, tile, overlap, winsize, iterations, poly_n, poly_sigma,
                           flags, flow_out, nullptr, nullptr, nullptr);
+}
+
+int ma_farneback_levels(ma_ctx* ctx, const void* prev, const void* next, int dtype, int H, int W, int levels,
+                        double pyr_scale, int winsize, int iterations, int poly_n, double poly_sigma, int flags,
+                        float* flow_out)
+{
+    return farneback_levels_impl(ctx, prev, next, dtype, H, W, levels, pyr_scale, winsize, iterations, poly_n, poly_sigma,
+                                 flags, flow_out);
 }
 
 int ma_farneback_debug(ma_ctx* ctx, const void* prev, const void* next, int dtype, int H, int W, int winsize,

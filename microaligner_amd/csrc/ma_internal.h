@@ -136,6 +136,8 @@ int ma_nmi_u8_enqueue2(ma_ctx* ctx, const uint8_t* a, const uint8_t* b0, const u
 int ma_ws_reserve(ma_ctx* ctx, size_t bytes);      // ensures ctx->ws has >= bytes
 // workspace one dog() call of an (h, w) image takes from ctx->ws (dog.hip)
 size_t ma_dog_workspace_bytes(int h, int w, int low_sigma);
+// getGaussianKernel(ksize, sigma, CV_32F): k[0 .. ksize) (dog.hip)
+void ma_gaussian_kernel(int ksize, double sigma, std::vector<float>& k);
 int ma_pinned_reserve(ma_ctx* ctx, size_t bytes);
 int ma_dconst_reserve(ma_ctx* ctx, size_t bytes);
 // immutable device copies of small float tables (filter taps), cached per (device, key) for the process lifetime

@@ -539,17 +539,25 @@ class Context:
         return out
 
     # -- primitives (device in, device out) ---------------------------------------------------
-    def farneback(self, prev, nxt, winsize, iterations, tile=0, overlap=0, poly_n=1, poly_sigma=1.7, fused=False):
+    def farneback(self, prev, nxt, winsize, iterations, tile=0, overlap=0, poly_n=1, poly_sigma=1.7, fused=False, levels=0):
         """cv2.calcOpticalFlowFarneback(prev, next, levels=0, GAUSSIAN) on the whole image (tile=0)
-        or on TileFlowCalc's overlapping windows, stitched (flow_calc.py:59-98)."""
+        or on TileFlowCalc's overlapping windows, stitched (flow_calc.py:59-98).  levels > 0: OpenCV's pyramid
+        (pyr_scale 0.5) on the whole image (ma_farneback_levels)."""
         if prev.shape != nxt.shape or prev.ndim != 2:
             raise ValueError("prev/next must be 2-D arrays of the same shape")
+        if levels > 0 and tile > 0:
+            raise ValueError("levels > 0 runs on the whole image: tile must be 0")
         if prev.dtype != nxt.dtype:
             # cv2.calcOpticalFlowFarneback converts each input to float32 on its own (exact for integers): a mixed pair
             # is the float32 pair
             prev, nxt = self.to_f32(prev), self.to_f32(nxt)
         H, W = prev.shape
         flow = self.empty((H, W, 2), np.float32)
+        if levels > 0:
+            self._run(self.lib.ma_farneback_levels, prev.ptr, nxt.ptr, _dt(prev.dtype), H, W, int(levels), 0.5,
+                      int(winsize), int(iterations), int(poly_n), float(poly_sigma),
+                      L.MA_FB_MULADD_FUSED if fused else 0, flow.ptr)
+            return flow
         self._run(self.lib.ma_farneback_tiled, prev.ptr, nxt.ptr, _dt(prev.dtype), H, W, int(tile),
                                             int(overlap), int(winsize), int(iterations), int(poly_n),
                                             float(poly_sigma), L.MA_FB_MULADD_FUSED if fused else 0, flow.ptr)

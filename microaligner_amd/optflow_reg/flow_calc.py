@@ -17,13 +17,13 @@ def _result(flow_dev, like):
 
 def farneback(mov_img, ref_img, pyr_size=0, win_size=51, num_iter=1, muladd_fused=False):
     """cv2.calcOpticalFlowFarneback(mov, ref, None, 0.5, pyr_size, win_size, num_iter, poly_n=1,
-    poly_sigma=1.7, OPTFLOW_FARNEBACK_GAUSSIAN) -- flow_calc.py:30-47.  Only the single-scale
-    form the reference uses (pyr_size == 0) exists on the device."""
-    if pyr_size != 0:
-        raise ValueError("only pyr_size == 0 (single scale, as microaligner calls it) is supported")
+    poly_sigma=1.7, OPTFLOW_FARNEBACK_GAUSSIAN) -- flow_calc.py:30-47.  pyr_size > 0 builds OpenCV's
+    pyramid on the device; levels below OpenCV's 32-px minimum are dropped as OpenCV drops them."""
+    if isinstance(pyr_size, (bool, np.bool_)) or not isinstance(pyr_size, (int, np.integer)) or pyr_size < 0:
+        raise ValueError(f"pyr_size must be a non-negative integer, got {pyr_size!r}")
     ctx = get_context()
     prev, nxt = ctx.asdevice(mov_img), ctx.asdevice(ref_img)
-    flow = ctx.farneback(prev, nxt, win_size, num_iter, tile=0, overlap=0, fused=muladd_fused)
+    flow = ctx.farneback(prev, nxt, win_size, num_iter, tile=0, overlap=0, fused=muladd_fused, levels=int(pyr_size))
     return _result(flow, mov_img)
 
 
