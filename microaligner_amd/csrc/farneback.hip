@@ -665,7 +665,8 @@ __global__ __launch_bounds__(64 * NW, BH_WAVES) void fb_blur_h_solve(FbGeom g, i
                     if (inside && !r1zero) {
                         float a00 = (1.f - fx) * (1.f - fy), a01 = fx * (1.f - fy), a10 = (1.f - fx) * fy,
                               a11 = fx * fy;
-                        // 0 <= y1 < Ph < 2^15 and pitch < 2^16 here: a 24-bit multiply-add (full rate) serves
+                        // inside means 0 <= y1 < Ph - 1, and check_window keeps Ph * pitch * 80 <= 2^31 - 1, so y1 and
+                        // pitch are below 2^31 / 160 < 2^24 here: a 24-bit multiply-add (full rate) serves
                         const int q0 = (int)(__umul24((unsigned)y1, (unsigned)g.pitch) + (unsigned)x1) * 4, q1 = q0 + pitch4;
 #pragma unroll
                         for (int k = 0; k < 5; k++) {
@@ -1209,6 +1210,17 @@ int get_taps(ma_ctx* ctx, int winsize, const float** out)
     return ma_const_table(ctx, ((uint64_t)1 << 56) | (uint64_t)winsize, t.data(), t.size(), out);
 }
 
+// The one size check of both paths: the 20 planes of a Ph x Pw window must be addressable with 32-bit byte offsets
+int check_window(int Ph, int Pw)
+{
+    const size_t bytes = ma_fb_window_bytes(Ph, Pw);
+    if (bytes <= MA_FB_WINDOW_MAX_BYTES) return MA_OK;
+    ma_set_error("invalid argument: Farneback window of %d x %d px too large: its 20 planes take %zu bytes, the 32-bit "
+                 "plane addressing allows %zu (5178 x 5178 is the largest square window)", Ph, Pw, bytes,
+                 MA_FB_WINDOW_MAX_BYTES);
+    return MA_EINVAL;
+}
+
 int farneback_impl(ma_ctx* ctx, const void* prev, const void* next, int dtype, int H, int W, int tile, int overlap,
                    int winsize, int iterations, int poly_n, double poly_sigma, int flags, float* flow_out,
                    float* R0_out, float* R1_out, float* M0_out)
@@ -1220,6 +1232,8 @@ int farneback_impl(ma_ctx* ctx, const void* prev, const void* next, int dtype, i
     MA_REQUIRE(winsize >= 1, "winsize must be >= 1");
     MA_REQUIRE(iterations >= 1, "iterations must be >= 1");
     MA_REQUIRE(poly_n == 1, "only poly_n == 1 is supported (the value microaligner passes)");
+    const MaTiling t = ma_make_tiling(H, W, tile, overlap);
+    MA_TRY(check_window(t.Ph, t.Pw));
     MA_HIP(hipSetDevice(ctx->device));
 
     PolyConsts pc;
@@ -1229,7 +1243,7 @@ int farneback_impl(ma_ctx* ctx, const void* prev, const void* next, int dtype, i
     const int m = winsize / 2;
 
     FbGeom g;
-    g.t = ma_make_tiling(H, W, tile, overlap);
+    g.t = t;
     g.pitch = (int)ma_align_up((size_t)g.t.Pw, 64);
     g.plane = (size_t)g.t.Ph * g.pitch;
     g.margin = 1 << 28;  // set per batch family in run_batch
@@ -1401,9 +1415,7 @@ int farneback_levels_impl(ma_ctx* ctx, const void* prev, const void* next, int d
     if (L.size() == 1)
         return farneback_impl(ctx, prev, next, dtype, H, W, 0, 0, winsize, iterations, poly_n, poly_sigma, flags, flow_out,
                               nullptr, nullptr, nullptr);
-    // the iteration kernels address a window's 20 planes with 32-bit byte offsets
-    MA_REQUIRE(level_geom(L[0]).plane * PL_COUNT * sizeof(float) <= (size_t)INT32_MAX,
-               "image too large for whole-image Farneback (20 planes of the finest level must stay below 2 GiB)");
+    MA_TRY(check_window(L[0].h, L[0].w));
     const FbLevelWs lw = level_workspace(L, H);
     MA_REQUIRE(lw.total * sizeof(float) <= ctx->ws_limit, "the finest level does not fit the workspace limit");
     MA_HIP(hipSetDevice(ctx->device));
@@ -1428,6 +1440,11 @@ int farneback_levels_impl(ma_ctx* ctx, const void* prev, const void* next, int d
 }
 
 } // namespace
+
+size_t ma_fb_window_bytes(int Ph, int Pw)
+{
+    return (size_t)Ph * ma_align_up((size_t)Pw, 64) * PL_COUNT * sizeof(float);
+}
 
 extern "C" {
 

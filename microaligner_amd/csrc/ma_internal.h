@@ -458,3 +458,9 @@ static inline MaTiling ma_make_tiling(int H, int W, int tile, int overlap)
     }
     return g;
 }
+
+// Bytes of the 20 float planes (Ph rows of align64(Pw) floats each) that Farneback keeps for one window.  Its window
+// kernels address them through one buffer resource with 32-bit byte offsets, so a window whose planes take more than
+// MA_FB_WINDOW_MAX_BYTES is refused (5178 x 5178 is the largest square window) -- farneback.hip.
+constexpr size_t MA_FB_WINDOW_MAX_BYTES = (size_t)INT32_MAX;
+size_t ma_fb_window_bytes(int Ph, int Pw);

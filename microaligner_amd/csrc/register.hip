@@ -218,6 +218,31 @@ int ma_optflow_register(ma_ctx* ctx, const void* ref, const void* mov, int dtype
                "Number of pyramid levels is 0 and use_full_res_img is False. Please change one of the parameters");
     MA_REQUIRE(p.num_pyr_lvl < 31, "too many pyramid levels");
     MA_REQUIRE(p.tile_size > 0 && p.overlap >= 0 && p.num_iterations >= 1, "bad tile_size / overlap / num_iterations");
+    // every level's Farneback window must fit the 32-bit plane addressing (ma_fb_window_bytes): refused before anything
+    // is enqueued.  The level sizes are build_pyramid's.
+    {
+        std::vector<std::pair<int, int>> sizes;
+        for (int l = 0, ch = H, cw = W; l < p.num_pyr_lvl; l++) {
+            const int factor = 1 << (l + 1);
+            if ((double)H / factor < 100. || (double)W / factor < 100.) break;
+            ch = (ch + 1) / 2; cw = (cw + 1) / 2;
+            sizes.emplace_back(ch, cw);
+        }
+        if (p.use_full_res_img) sizes.emplace_back(H, W);
+        for (const auto& s : sizes) {
+            const bool tiled = is_tiled(s.first, s.second, p.tile_size);
+            const int ph = tiled ? p.tile_size + 2 * p.overlap : s.first, pw = tiled ? p.tile_size + 2 * p.overlap : s.second;
+            const size_t bytes = ma_fb_window_bytes(ph, pw);
+            if (bytes > MA_FB_WINDOW_MAX_BYTES) {
+                ma_set_error("invalid argument: tile_size=%d, overlap=%d: the level of %d x %d px runs Farneback on %s "
+                             "window of %d x %d px, whose 20 planes take %zu bytes; the 32-bit plane addressing allows %zu "
+                             "(5178 x 5178 is the largest square window).  A level is tiled when its longer side is at "
+                             "least 2 * tile_size", p.tile_size, p.overlap, s.first, s.second, tiled ? "each" : "one whole",
+                             ph, pw, bytes, MA_FB_WINDOW_MAX_BYTES);
+                return MA_EINVAL;
+            }
+        }
+    }
     if (n_reports) *n_reports = 0;
     MA_HIP(hipSetDevice(ctx->device));
 

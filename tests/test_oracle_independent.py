@@ -9,11 +9,17 @@ What it does NOT pin: last bits (OpenCV's summation order, float32 intermediates
 (tests/test_cv2_golden.py, tests/test_cv2_parity.py), which this image and the GPU pool do not have.  Tolerances are stated
 per test.  Reference call sites: optflow_reg/flow_calc.py:33-44, optflow_reg/warper.py:56-66,
 optflow_reg/optflow_registrator.py:45,140-214."""
+import os
+import sys
+
 import numpy as np
 import pytest
 from scipy import ndimage as ndi
 
 from oracle import oracle as O
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _f64_ref import dog_float64, farneback_float64  # noqa: E402
 
 
 def _texture(h, w, seed, amp=100.0):
@@ -124,49 +130,6 @@ def test_pyr_up_is_zero_insertion_times_four_through_the_same_kernel(src, dst):
 
 
 # ---- cv2.calcOpticalFlowFarneback(levels=0, poly_n=1, poly_sigma=1.7, OPTFLOW_FARNEBACK_GAUSSIAN) ------------------
-def _poly_expansion(img, n=1, sigma=1.7):
-    """Farneback 2003, section 2: per pixel the weighted least-squares fit  f(x) ~ x'Ax + b'x + c  over a (2n+1)^2
-    neighbourhood with a Gaussian applicability.  Returns c, bx, by, axx, ayy, axy (axy = coefficient of x*y)."""
-    xs = np.arange(-n, n + 1, dtype=np.float64)
-    g = np.exp(-xs ** 2 / (2 * sigma ** 2))
-    X, Y = np.meshgrid(xs, xs)                                 # X varies along columns
-    B = np.stack([np.ones_like(X), X, Y, X * X, Y * Y, X * Y], -1).reshape(-1, 6)
-    Wa = np.outer(g, g).reshape(-1)
-    proj = np.linalg.inv(B.T @ (Wa[:, None] * B)) @ (B.T * Wa)  # 6 x (2n+1)^2
-    return [ndi.correlate(img, proj[k].reshape(2 * n + 1, 2 * n + 1), mode="nearest") for k in range(6)]
-
-
-def _farneback_float64(prev, nxt, winsize, iterations, det_eps=0.0):
-    """Displacement estimation of the paper's sections 4 - 5 (eqs. 7 - 11 with the a-priori displacement of section 5,
-    iterated), float64 throughout.  OpenCV specifics that are PARAMETERS of the call, not of the paper, taken from the
-    call site: 3 x 3 binomial pre-smoothing of both images at pyramid scale 1, a Gaussian window of sigma = 0.3 * (winsize
-    // 2), the second expansion sampled bilinearly at x + d.  Not modelled: OpenCV's border attenuation (5 px) -- compare away
-    from borders.  det_eps: OpenCV adds 1e-3 to the determinant of the 2 x 2 system (a regulariser the paper does not have);
-    0 is the paper."""
-    pre = lambda im: ndi.correlate1d(ndi.correlate1d(im.astype(np.float64), [0.25, 0.5, 0.25], axis=0, mode="mirror"),
-                                     [0.25, 0.5, 0.25], axis=1, mode="mirror")
-    c0, bx0, by0, axx0, ayy0, axy0 = _poly_expansion(pre(prev))
-    r1 = _poly_expansion(pre(nxt))
-    h, w = prev.shape
-    gx, gy = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
-    m = winsize // 2
-    k = np.exp(-np.arange(-m, m + 1) ** 2 / (2 * (m * 0.3) ** 2))
-    k /= k.sum()
-    blur = lambda a: ndi.correlate1d(ndi.correlate1d(a, k, axis=0, mode="nearest"), k, axis=1, mode="nearest")
-    dx, dy = np.zeros((h, w)), np.zeros((h, w))
-    for _ in range(iterations):
-        s = [ndi.map_coordinates(p, [gy + dy, gx + dx], order=1, mode="nearest") for p in r1]
-        _, bx1, by1, axx1, ayy1, axy1 = s
-        a11, a22, a12 = (axx0 + axx1) / 2, (ayy0 + ayy1) / 2, (axy0 + axy1) / 4       # A = (A1 + A2) / 2, A12 = axy / 2
-        dbx = -0.5 * (bx1 - bx0) + a11 * dx + a12 * dy                                # eq. 10 with the a-priori d
-        dby = -0.5 * (by1 - by0) + a12 * dx + a22 * dy
-        g11, g12, g22 = blur(a11 * a11 + a12 * a12), blur(a12 * (a11 + a22)), blur(a12 * a12 + a22 * a22)
-        h1, h2 = blur(a11 * dbx + a12 * dby), blur(a12 * dbx + a22 * dby)
-        det = g11 * g22 - g12 * g12 + det_eps
-        dx, dy = (g22 * h1 - g12 * h2) / det, (g11 * h2 - g12 * h1) / det             # eq. 9: d = (sum w A'A)^-1 sum w A'db
-    return np.stack([dx, dy], -1)
-
-
 @pytest.mark.parametrize("winsize,iterations,shift,hw", [(15, 3, (1.3, -0.7), (110, 128)), (21, 2, (-0.6, 0.9), (110, 128)),
                                                          (9, 3, (0.4, 0.3), (110, 128)),
                                                          (99, 3, (2.2, -1.4), (400, 430))])   # the reference's window and iterations
@@ -183,10 +146,10 @@ def test_farneback_equals_the_papers_normal_equations_in_float64(winsize, iterat
     inner = lambda a: a[b:-b, b:-b]
     # (a) the paper as it stands: the only difference left is OpenCV's 1e-3 on the determinant, which matters where a
     #     small window sees little texture
-    d = np.abs(inner(got) - inner(_farneback_float64(prev, nxt, winsize, iterations)))
+    d = np.abs(inner(got) - inner(farneback_float64(prev, nxt, winsize, iterations)))
     assert np.median(d) <= 2e-4 and d.max() <= (1e-3 if winsize >= 15 else 5e-3), f"paper: max {d.max():.2e} px"
     # (b) with that one documented constant the float32 oracle IS the float64 normal equations (measured: 3e-6 px)
-    d = np.abs(inner(got) - inner(_farneback_float64(prev, nxt, winsize, iterations, det_eps=1e-3)))
+    d = np.abs(inner(got) - inner(farneback_float64(prev, nxt, winsize, iterations, det_eps=1e-3)))
     assert d.max() <= 2e-5, f"max |oracle - float64 normal equations| = {d.max():.2e} px"
     # and the estimate is the displacement that was applied: direction, channel order (x first), magnitude
     med = np.median(got[b:-b, b:-b].reshape(-1, 2), axis=0)
@@ -225,16 +188,23 @@ def test_dog_chain_in_float64(dtype, top):
     high - low -> normalize to [0, 255] uint8, restated with scipy in float64 (kernel taps from the definition, truncated at the
     41-tap window and renormalised): the oracle's uint8 image within one grey level, equal at > 97 % of the pixels."""
     img = (_texture(180, 210, 41, 1.0) * top).astype(dtype)
-    f = img.astype(np.float64)
-    f = (f - f.min()) / (f.max() - f.min())
-
-    def blur(a, sigma, ksize=41):
-        x = np.arange(ksize) - ksize // 2
-        k = np.exp(-x ** 2 / (2.0 * sigma ** 2))
-        k /= k.sum()
-        return ndi.correlate1d(ndi.correlate1d(a, k, axis=0, mode="mirror"), k, axis=1, mode="mirror")
-    d = blur(f, 9) - blur(f, 5)
-    exp = np.rint((d - d.min()) / (d.max() - d.min()) * 255)
+    exp = dog_float64(img)
     got = O.dog(img, True).astype(np.float64)
     assert O.dog(img, True).dtype == np.uint8
     assert np.abs(got - exp).max() <= 1 and (got == exp).mean() > 0.97
+
+
+@pytest.mark.parametrize("sigmas", [(5, 9), (3, 5)])
+@pytest.mark.parametrize("dtype,top", [(np.uint8, 255), (np.uint16, 60000), (np.float32, 1.0)])
+def test_dog_chain_in_float64_when_the_border_folds_more_than_once(dtype, top, sigmas):
+    """Sides of 20 px or less: the 41-tap (sigmas 5 / 9) and 25-tap (3 / 5) windows reach past the far border, and
+    reflect-101 folds again (scipy's mode="mirror" at any fold count).  Within one grey level everywhere; measured: every
+    pixel equal, so at most one differing pixel is allowed (on 35 pixels one is already 3 %)."""
+    for h, w in [(1, 2), (2, 1), (1, 20), (20, 1), (2, 3), (3, 19), (19, 20), (20, 20), (5, 7)]:
+        img = (_texture(h, w, 100 * h + w, 1.0) * top).astype(dtype)
+        if img.max() == img.min():
+            continue
+        exp = dog_float64(img, *sigmas)
+        got = O.dog(img, True, *sigmas).astype(np.float64)
+        d = np.abs(got - exp)
+        assert d.max() <= 1 and (d > 0).sum() <= 1, (h, w)

@@ -6,7 +6,8 @@ Per (size, window, pyr_size): the median over `reps` calls of device-event time 
 the same shape), the ratio to pyr_size 0, and the library's per-kernel accounting (ma_profile_*) of one call.  For the
 level-image kernel (blur + resize of both inputs, MA_K_FB_LEVEL_IMG) it also gives the HBM bytes it must move -- one read
 of each input, the row pass written and read back, the level image written -- over its time, against 8 TB/s.
-Whole-image Farneback keeps a level's 20 planes below 2 GiB: 5120^2 is the largest square it takes (8192^2 is refused).
+Whole-image Farneback keeps a window's 20 planes (rows padded to 64 floats) within INT32_MAX bytes: 5178^2 is the largest
+square image it takes (8192^2 is refused with ValueError, at every pyr_size).
 Prints one JSON line."""
 import argparse
 import json
