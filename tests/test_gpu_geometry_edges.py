@@ -82,6 +82,22 @@ def test_untiled_farneback_is_the_float64_normal_equations_in_the_interior(ctx, 
     assert np.abs(np.median(got[b:-b, b:-b].reshape(-1, 2), axis=0) - (1.3, -0.7)).max() < 0.1
 
 
+@pytest.mark.parametrize("shape", [(113, 129), (129, 113)])
+def test_untiled_farneback_is_the_float64_statement_over_the_whole_image(ctx, shape):
+    """The sibling of the interior test on the whole image, border band included: with OpenCV's border rules (the
+    out-of-range rule of UpdateMatrices and the 5-px attenuation) the float64 statement holds up to the last pixel.
+    Measured on the oracle (bit-exact to the kernels): 99th percentile 1.4e-6 px, max 4.9e-6 px."""
+    h, w = shape
+    win, iters = 15, 3
+    prev, nxt = shifted_texture_pair(h, w, h + w, (1.3, -0.7))
+    exp = farneback_float64(prev, nxt, win, iters, det_eps=1e-3, opencv_borders=True)
+    for fused in (False, True):
+        got = ctx.farneback(ctx.asdevice(prev), ctx.asdevice(nxt), win, iters, fused=fused).numpy()
+        d = np.abs(got - exp).max(-1)
+        assert np.quantile(d, 0.99) <= 5e-6 and d.max() <= 1.5e-5, \
+            f"fused={fused}: 99th percentile {np.quantile(d, 0.99):.2e} px, max {d.max():.2e} px"
+
+
 # ---- B. tiled Farneback -----------------------------------------------------------------------------------------------
 # W, H = k * tile + r: ragged last tiles of 1, 2, 31, 32 and 33 px; overlap 0 (windows of exactly one tile), 1 and a
 # regular one
