@@ -147,6 +147,14 @@ QC_SIGNATURES = {
                              C.POINTER(_d), C.POINTER(_d)]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_interp.h (cv2.remap's other interpolation modes)
+MA_INTER_NEAREST, MA_INTER_LINEAR, MA_INTER_CUBIC, MA_INTER_LANCZOS4 = 0, 1, 2, 4   # enum ma_interp
+INTERP_SIGNATURES = {
+    "ma_remap_interp": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i]),
+    "ma_warp_tiled_interp": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i]),
+    "ma_warp_pages_host_interp": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp, _i, _i, _i]),
+}
+
 _lib = None
 
 
@@ -160,7 +168,7 @@ def load():
             f"{LIB_PATH} not found: build the HIP extension first (python -m microaligner_amd.build). "
             "microaligner_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

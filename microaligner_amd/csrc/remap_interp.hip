@@ -1,0 +1,632 @@
+// cv2.remap's INTER_NEAREST, INTER_CUBIC and INTER_LANCZOS4 (include/microaligner_interp.h) for the generic remap, the
+// tiled warp of Warper.warp() and the page-warp driver.  Off the measured path: remap.hip keeps the linear kernels, and
+// MA_INTER_LINEAR forwards to them.
+//
+// Coordinates are quantised as remap.hip's quantise() does (1/32 px, cvRound); nearest rounds each coordinate on its own.
+// The 1-D weight tables are built once per device on the host (interpolateCubic in float, interpolateLanczos4 with sin /
+// cos in double) and staged in LDS by every block; u8 forms its 15-bit 2-D weights from them plus the one correction of
+// initInterTab2D's sum fix-up, a (tap, delta) pair per fraction pair.  Every sample picks OpenCV's summation order: all
+// taps inside the source -> rows left to right, then the row sums; otherwise the taps inside the source one by one.
+// Direct gathers, as the linear kernels: several rows per thread, a wave-wide "all taps inside window and image" vote
+// selects a straight-line path whose loads are all issued before the first sum.
+#include "ma_internal.h"
+#include "../../include/microaligner_interp.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <condition_variable>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+namespace {
+
+constexpr int TAB = 32;   // INTER_TAB_SIZE
+
+__constant__ float c_tab_cubic[TAB * 4];
+__constant__ float c_tab_lanczos[TAB * 8];
+// per fraction pair fy * 32 + fx: tap index | (delta << 8) of initInterTab2D's fix-up of the u8 table (delta 0: none)
+__constant__ int c_fix_cubic[TAB * TAB];
+__constant__ int c_fix_lanczos[TAB * TAB];
+
+template <int MODE> struct Mode;
+template <> struct Mode<MA_INTER_NEAREST> { static constexpr int N = 1, OFF = 0, R = 8; };
+template <> struct Mode<MA_INTER_CUBIC> { static constexpr int N = 4, OFF = 1, R = 4; };
+template <> struct Mode<MA_INTER_LANCZOS4> { static constexpr int N = 8, OFF = 3, R = 2; };
+
+template <int N> __device__ __forceinline__ const float* d_tab1() { return N == 4 ? c_tab_cubic : c_tab_lanczos; }
+template <int N> __device__ __forceinline__ const int* d_fix() { return N == 4 ? c_fix_cubic : c_fix_lanczos; }
+
+__device__ __forceinline__ short d_sat_short(int v) { return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
+// (unsigned)v < max(n, 0): OpenCV's width1 tests
+__device__ __forceinline__ bool d_below(int v, int n) { return n > 0 && (unsigned)v < (unsigned)n; }
+
+struct Tap {
+    int sx, sy;   // integer source coordinate (before the tap offset)
+    int fx, fy;   // 5-bit fractions
+};
+__device__ __forceinline__ Tap quantise(float mx, float my)
+{
+    int sxq = d_cvround(mx * 32.f), syq = d_cvround(my * 32.f);
+    Tap t;
+    t.fx = sxq & 31; t.fy = syq & 31;
+    t.sx = d_sat_short(sxq >> 5); t.sy = d_sat_short(syq >> 5);
+    return t;
+}
+
+// stage the 1-D table of the mode in LDS (every thread of the block takes part: before any early return)
+template <int N>
+__device__ __forceinline__ void load_tab(float* s_tab)
+{
+    if (N > 1) {
+        for (int i = threadIdx.x; i < TAB * N; i += blockDim.x) s_tab[i] = d_tab1<N>()[i];
+        __syncthreads();
+    }
+}
+
+// One sample from its N x N taps v (0 where a tap is not read).  fast: every tap lies inside the source (OpenCV's
+// straight path); otherwise rmask / cmask hold the rows / columns of taps inside the source, and only those are summed.
+template <typename T, int N>
+__device__ __forceinline__ T combine(const T (&v)[N][N], const float* s_tab, int fx, int fy, bool fast, unsigned rmask,
+                                     unsigned cmask)
+{
+    float wx[N], wy[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) { wx[k] = s_tab[fx * N + k]; wy[k] = s_tab[fy * N + k]; }
+    if constexpr (sizeof(T) == 1) {
+        // integer sum: the order does not matter, and taps outside the source hold 0
+        const int fix = d_fix<N>()[fy * TAB + fx], ftap = fix & 255, fdel = fix >> 8;
+        int acc = 0;
+#pragma unroll
+        for (int k1 = 0; k1 < N; k1++)
+#pragma unroll
+            for (int k2 = 0; k2 < N; k2++) {
+                const float p = wy[k1] * wx[k2];
+                const int w = d_sat_short(d_cvround(p * 32768.f)) + (k1 * N + k2 == ftap ? fdel : 0);
+                acc += (int)v[k1][k2] * w;
+            }
+        return (T)d_clamp((acc + (1 << 14)) >> 15, 0, 255);
+    } else {
+        float sum = 0.f;
+        if (fast) {
+#pragma unroll
+            for (int k1 = 0; k1 < N; k1++) {
+                float r = (float)v[k1][0] * (wy[k1] * wx[0]);
+#pragma unroll
+                for (int k2 = 1; k2 < N; k2++) r = r + (float)v[k1][k2] * (wy[k1] * wx[k2]);
+                // remapBicubic starts from the first row sum, remapLanczos4 from 0
+                sum = (N == 4 && k1 == 0) ? r : sum + r;
+            }
+        } else {
+#pragma unroll
+            for (int k1 = 0; k1 < N; k1++)
+#pragma unroll
+                for (int k2 = 0; k2 < N; k2++)
+                    if ((rmask >> k1) & (cmask >> k2) & 1u) sum = sum + (float)v[k1][k2] * (wy[k1] * wx[k2]);
+        }
+        if constexpr (sizeof(T) == 2) return (T)d_clamp(d_cvround(sum), 0, 65535);
+        else return sum;
+    }
+}
+
+// ---- generic cv2.remap --------------------------------------------------------------------------------------------
+template <typename T, int MODE, int CN>
+__global__ __launch_bounds__(256) void remap_interp_kernel(const T* __restrict__ src, int sh, int sw,
+                                                           const float2* __restrict__ map, int dh, int dw,
+                                                           T* __restrict__ dst)
+{
+    constexpr int N = Mode<MODE>::N, OFF = Mode<MODE>::OFF;
+    __shared__ float s_tab[TAB * N];
+    load_tab<N>(s_tab);
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= dw) return;
+    const float2 m = map[(size_t)y * dw + x];
+    T out[CN];
+#pragma unroll
+    for (int c = 0; c < CN; c++) out[c] = (T)0;
+    if constexpr (MODE == MA_INTER_NEAREST) {
+        const int X = d_sat_short(d_cvround(m.x)), Y = d_sat_short(d_cvround(m.y));
+        if ((unsigned)X < (unsigned)sw && (unsigned)Y < (unsigned)sh) {
+#pragma unroll
+            for (int c = 0; c < CN; c++) out[c] = src[((size_t)Y * sw + X) * CN + c];
+        }
+    } else {
+        const Tap t = quantise(m.x, m.y);
+        const int sx = t.sx - OFF, sy = t.sy - OFF;
+        if (!(sx >= sw || sx + N <= 0 || sy >= sh || sy + N <= 0)) {
+            const bool fast = d_below(sx, sw - N + 1) && d_below(sy, sh - N + 1);
+            unsigned rmask = 0, cmask = 0;
+#pragma unroll
+            for (int k = 0; k < N; k++) {
+                rmask |= (unsigned)((unsigned)(sy + k) < (unsigned)sh) << k;
+                cmask |= (unsigned)((unsigned)(sx + k) < (unsigned)sw) << k;
+            }
+#pragma unroll
+            for (int c = 0; c < CN; c++) {
+                T v[N][N];
+#pragma unroll
+                for (int k1 = 0; k1 < N; k1++)
+#pragma unroll
+                    for (int k2 = 0; k2 < N; k2++)
+                        v[k1][k2] = ((rmask >> k1) & (cmask >> k2) & 1u) ? src[((size_t)(sy + k1) * sw + (sx + k2)) * CN + c]
+                                                                          : (T)0;
+                out[c] = combine<T, N>(v, s_tab, t.fx, t.fy, fast, rmask, cmask);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < CN; c++) dst[((size_t)y * dw + x) * CN + c] = out[c];
+}
+
+// ---- Warper.warp(): window-local map = float(x_local) - flow, the zero-padded window is the source ------------------
+// Window origins, as remap.hip states them for the linear kernels (restated here, not shared, so that remap.hip stays
+// as the measured path has it).
+__device__ __forceinline__ int warp_window_origin_x(int x, const MaTiling& g)
+{
+    if (g.T <= 0) return 0;
+    if (g.T < 64) return (x / g.T) * g.T - g.ov;
+    const int x_first = __builtin_amdgcn_readfirstlane(x - (int)(threadIdx.x & 63));
+    const int t0 = x_first / g.T, next = (t0 + 1) * g.T;
+    return (x >= next ? next : t0 * g.T) - g.ov;
+}
+struct WarpRowsY {
+    int t0T, next, T, ov;
+    __device__ __forceinline__ WarpRowsY(int y0, const MaTiling& g) : T(g.T), ov(g.ov)
+    {
+        const int t0 = g.T > 0 ? y0 / g.T : 0;
+        t0T = t0 * g.T; next = t0T + g.T;
+    }
+    __device__ __forceinline__ int origin(int y) const
+    {
+        if (T <= 0) return 0;
+        if (T < 16) return (y / T) * T - ov;
+        return (y >= next ? next : t0T) - ov;
+    }
+};
+
+// one sample of the window at (ox, oy), tap origin (sx, sy) window-local: taps beyond the window are not read (skipped
+// by the sum unless every tap is inside it), taps in the window's zero padding read 0
+template <typename T, int N>
+__device__ __forceinline__ T warp_interp_px(const T* __restrict__ img, const MaTiling& g, const Tap& t, int sx, int sy,
+                                            int ox, int oy, const float* s_tab)
+{
+    if (sx >= g.Pw || sx + N <= 0 || sy >= g.Ph || sy + N <= 0) return (T)0;
+    const bool fast = d_below(sx, g.Pw - N + 1) && d_below(sy, g.Ph - N + 1);
+    unsigned rmask = 0, cmask = 0, rimg = 0, cimg = 0;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        rmask |= (unsigned)((unsigned)(sy + k) < (unsigned)g.Ph) << k;
+        cmask |= (unsigned)((unsigned)(sx + k) < (unsigned)g.Pw) << k;
+        rimg |= (unsigned)((unsigned)(oy + sy + k) < (unsigned)g.H) << k;
+        cimg |= (unsigned)((unsigned)(ox + sx + k) < (unsigned)g.W) << k;
+    }
+    const unsigned rok = rmask & rimg, cok = cmask & cimg;
+    T v[N][N];
+#pragma unroll
+    for (int k1 = 0; k1 < N; k1++)
+#pragma unroll
+        for (int k2 = 0; k2 < N; k2++)
+            v[k1][k2] = ((rok >> k1) & (cok >> k2) & 1u) ? img[(size_t)(oy + sy + k1) * g.W + (ox + sx + k2)] : (T)0;
+    return combine<T, N>(v, s_tab, t.fx, t.fy, fast, rmask, cmask);
+}
+
+// Output rows [y_begin, y_end) of the tiled warp (the whole image for ma_warp_tiled_interp, one band for the page driver).
+// R rows per thread; block rows beyond the grid's y extent loop (gridDim.y is capped).
+template <typename T, int MODE, bool IDX32>
+__global__ __launch_bounds__(256) void warp_interp_kernel(const T* __restrict__ img, MaTiling g,
+                                                          const float2* __restrict__ flow, T* __restrict__ out,
+                                                          int y_begin, int y_end)
+{
+    constexpr int N = Mode<MODE>::N, OFF = Mode<MODE>::OFF, R = Mode<MODE>::R;
+    __shared__ float s_tab[TAB * N];
+    load_tab<N>(s_tab);
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int ox = warp_window_origin_x(min(x, g.W - 1), g);     // (all lanes: the wave's first lane decides)
+    if (x >= g.W) return;
+    const int lx = x - ox;
+    for (int y0 = y_begin + (int)blockIdx.y * R; y0 < y_end; y0 += (int)gridDim.y * R) {
+        const WarpRowsY rows(y0, g);
+        float2 f[R];
+        int ys[R], oys[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            ys[r] = min(y0 + r, y_end - 1);
+            oys[r] = rows.origin(ys[r]);
+            f[r] = flow[(size_t)ys[r] * g.W + x];
+        }
+        T res[R];
+        if constexpr (MODE == MA_INTER_NEAREST) {
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                // warper.py:57-59: float32(float64(-flow) + arange) == the correctly rounded lx - flow
+                const int X = d_sat_short(d_cvround((float)lx - f[r].x)), Y = d_sat_short(d_cvround((float)(ys[r] - oys[r]) - f[r].y));
+                const int jx = ox + X, jy = oys[r] + Y;
+                const bool ok = (unsigned)X < (unsigned)g.Pw && (unsigned)Y < (unsigned)g.Ph && (unsigned)jx < (unsigned)g.W &&
+                                (unsigned)jy < (unsigned)g.H;
+                res[r] = ok ? img[(size_t)jy * g.W + jx] : (T)0;
+            }
+        } else {
+            Tap t[R];
+            int sx[R], sy[R];
+            bool inside = true;
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                t[r] = quantise((float)lx - f[r].x, (float)(ys[r] - oys[r]) - f[r].y);
+                sx[r] = t[r].sx - OFF; sy[r] = t[r].sy - OFF;
+                inside = inside && d_below(sx[r], g.Pw - N + 1) && d_below(sy[r], g.Ph - N + 1) &&
+                         d_below(ox + sx[r], g.W - N + 1) && d_below(oys[r] + sy[r], g.H - N + 1);
+            }
+            if (__all(inside)) {
+                // every tap of every row of the wave inside both window and image: OpenCV's straight path, loads first
+                T v[R][N][N];
+#pragma unroll
+                for (int r = 0; r < R; r++) {
+                    if (IDX32) {
+                        const unsigned p = (unsigned)(oys[r] + sy[r]) * (unsigned)g.W + (unsigned)(ox + sx[r]);
+#pragma unroll
+                        for (int k1 = 0; k1 < N; k1++)
+#pragma unroll
+                            for (int k2 = 0; k2 < N; k2++) v[r][k1][k2] = img[p + (unsigned)k1 * (unsigned)g.W + (unsigned)k2];
+                    } else {
+                        const T* q = img + (size_t)(oys[r] + sy[r]) * g.W + (ox + sx[r]);
+#pragma unroll
+                        for (int k1 = 0; k1 < N; k1++)
+#pragma unroll
+                            for (int k2 = 0; k2 < N; k2++) v[r][k1][k2] = q[(size_t)k1 * g.W + k2];
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < R; r++) res[r] = combine<T, N>(v[r], s_tab, t[r].fx, t[r].fy, true, ~0u, ~0u);
+            } else {
+#pragma unroll
+                for (int r = 0; r < R; r++) res[r] = warp_interp_px<T, N>(img, g, t[r], sx[r], sy[r], ox, oys[r], s_tab);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; r++)
+            if (y0 + r < y_end) out[(size_t)(y0 + r) * g.W + x] = res[r];
+    }
+}
+
+// ---- host tables ----------------------------------------------------------------------------------------------------
+int h_cvround(float v)
+{
+    if (!(fabsf(v) < 2147483648.0f)) return INT_MIN;
+    return (int)lrintf(v);
+}
+short h_sat_short(int v) { return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
+
+// imgwarp.cpp interpolateCubic / interpolateLanczos4
+void interpolate_cubic(float x, float* coeffs)
+{
+    const float A = -0.75f;
+    coeffs[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
+    coeffs[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
+    coeffs[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
+    coeffs[3] = 1.f - coeffs[0] - coeffs[1] - coeffs[2];
+}
+void interpolate_lanczos4(float x, float* coeffs)
+{
+    static const double s45 = 0.70710678118654752440084436210485;
+    static const double cs[][2] = {{1, 0}, {-s45, -s45}, {0, 1}, {s45, -s45}, {-1, 0}, {s45, s45}, {0, -1}, {-s45, s45}};
+    const double PI = 3.1415926535897932384626433832795;
+    float sum = 0;
+    double y0 = -(x + 3) * PI * 0.25, s0 = std::sin(y0), c0 = std::cos(y0);
+    for (int i = 0; i < 8; i++) {
+        float y0_ = (x + 3 - i);
+        if (fabs(y0_) >= 1e-6f) {
+            double y = -y0_ * PI * 0.25;
+            coeffs[i] = (float)((cs[i][0] * s0 + cs[i][1] * c0) / (y * y));
+        } else {
+            coeffs[i] = 1e30f;
+        }
+        sum += coeffs[i];
+    }
+    sum = 1.f / sum;
+    for (int i = 0; i < 8; i++) coeffs[i] *= sum;
+}
+
+// initInterTab2D's u8 table for an N-tap 1-D table, reduced to the one entry its sum fix-up changes per fraction pair
+template <int N>
+void fix_table(const float* tab1, int* fix)
+{
+    for (int i = 0; i < TAB; i++)
+        for (int j = 0; j < TAB; j++) {
+            short itab[N * N], raw[N * N];
+            int isum = 0;
+            for (int k1 = 0; k1 < N; k1++) {
+                const float vy = tab1[i * N + k1];
+                for (int k2 = 0; k2 < N; k2++) {
+                    const float v = vy * tab1[j * N + k2];
+                    isum += itab[k1 * N + k2] = raw[k1 * N + k2] = h_sat_short(h_cvround(v * 32768));
+                }
+            }
+            if (isum != 32768) {
+                const int diff = isum - 32768, k = N / 2;
+                int Mk1 = k, Mk2 = k, mk1 = k, mk2 = k;
+                for (int k1 = k; k1 < k + 2; k1++)
+                    for (int k2 = k; k2 < k + 2; k2++) {
+                        if (itab[k1 * N + k2] < itab[mk1 * N + mk2]) mk1 = k1, mk2 = k2;
+                        else if (itab[k1 * N + k2] > itab[Mk1 * N + Mk2]) Mk1 = k1, Mk2 = k2;
+                    }
+                if (diff < 0) itab[Mk1 * N + Mk2] = (short)(itab[Mk1 * N + Mk2] - diff);
+                else itab[mk1 * N + mk2] = (short)(itab[mk1 * N + mk2] - diff);
+            }
+            int f = 0;
+            for (int t = 0; t < N * N; t++)
+                if (itab[t] != raw[t]) f = t | ((itab[t] - raw[t]) * 256);
+            fix[i * TAB + j] = f;
+        }
+}
+
+struct HostTables {
+    float cubic[TAB * 4], lanczos[TAB * 8];
+    int fix_cubic[TAB * TAB], fix_lanczos[TAB * TAB];
+    HostTables()
+    {
+        const float scale = 1.f / TAB;
+        for (int i = 0; i < TAB; i++) {
+            interpolate_cubic(i * scale, cubic + i * 4);
+            interpolate_lanczos4(i * scale, lanczos + i * 8);
+        }
+        fix_table<4>(cubic, fix_cubic);
+        fix_table<8>(lanczos, fix_lanczos);
+    }
+};
+
+// the tables reach a device's constant memory once, on the stream of the first ctx that needs them there
+int ensure_tables(ma_ctx* ctx)
+{
+    static const HostTables tabs;
+    static std::mutex mu;
+    static std::vector<char> ready;
+    std::lock_guard<std::mutex> lk(mu);
+    if ((int)ready.size() <= ctx->device) ready.resize(ctx->device + 1, 0);
+    if (ready[ctx->device]) return MA_OK;
+    MA_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_tab_cubic), tabs.cubic, sizeof(tabs.cubic), 0, hipMemcpyHostToDevice, ctx->stream));
+    MA_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_tab_lanczos), tabs.lanczos, sizeof(tabs.lanczos), 0, hipMemcpyHostToDevice, ctx->stream));
+    MA_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_fix_cubic), tabs.fix_cubic, sizeof(tabs.fix_cubic), 0, hipMemcpyHostToDevice, ctx->stream));
+    MA_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_fix_lanczos), tabs.fix_lanczos, sizeof(tabs.fix_lanczos), 0, hipMemcpyHostToDevice, ctx->stream));
+    MA_HIP(hipStreamSynchronize(ctx->stream));
+    ready[ctx->device] = 1;
+    return MA_OK;
+}
+
+bool interp_known(int interp)
+{
+    return interp == MA_INTER_NEAREST || interp == MA_INTER_LINEAR || interp == MA_INTER_CUBIC || interp == MA_INTER_LANCZOS4;
+}
+int rows_per_thread(int interp)
+{
+    return interp == MA_INTER_CUBIC ? Mode<MA_INTER_CUBIC>::R : interp == MA_INTER_LANCZOS4 ? Mode<MA_INTER_LANCZOS4>::R
+                                                                                           : Mode<MA_INTER_NEAREST>::R;
+}
+
+// the warp kernel over output rows [y0, y1) of an (H, W) image on the ctx stream (interp: nearest / cubic / lanczos4)
+int launch_warp(ma_ctx* ctx, const void* img, int dtype, const MaTiling& g, const float2* flow, void* out, int y0, int y1,
+                int interp)
+{
+    const int R = rows_per_thread(interp);
+    const int by = std::min((y1 - y0 + R - 1) / R, MA_GRID_Y_MAX);
+    const dim3 grid((g.W + 255) / 256, by), block(256);
+    const bool idx32 = (unsigned long long)g.H * (unsigned long long)g.W < (1ull << 31);
+#define MA_WI(T, M) do { if (idx32) hipLaunchKernelGGL((warp_interp_kernel<T, M, true>), grid, block, 0, ctx->stream, (const T*)img, g, flow, (T*)out, y0, y1); \
+                         else hipLaunchKernelGGL((warp_interp_kernel<T, M, false>), grid, block, 0, ctx->stream, (const T*)img, g, flow, (T*)out, y0, y1); } while (0)
+#define MA_WI_T(T) do { if (interp == MA_INTER_NEAREST) MA_WI(T, MA_INTER_NEAREST); else if (interp == MA_INTER_CUBIC) MA_WI(T, MA_INTER_CUBIC); \
+                        else MA_WI(T, MA_INTER_LANCZOS4); } while (0)
+    if (dtype == MA_U8) MA_WI_T(uint8_t);
+    else if (dtype == MA_U16) MA_WI_T(uint16_t);
+    else MA_WI_T(float);
+#undef MA_WI_T
+#undef MA_WI
+    MA_HIP(hipGetLastError());
+    return MA_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ma_remap_interp(ma_ctx* ctx, const void* src, int dtype, int cn, int sh, int sw, const float* map_xy, int dh, int dw,
+                    void* dst, int interp)
+{
+    MA_REQUIRE(interp_known(interp), "interp must be MA_INTER_NEAREST, _LINEAR, _CUBIC or _LANCZOS4");
+    if (interp == MA_INTER_LINEAR) return ma_remap_bilinear(ctx, src, dtype, cn, sh, sw, map_xy, dh, dw, dst);
+    MA_REQUIRE(ctx && src && map_xy && dst, "NULL argument");
+    MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
+    MA_REQUIRE(cn >= 1 && cn <= 4, "cn must be 1 to 4");
+    MA_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "empty image");
+    MA_REQUIRE(sh < 32767 && sw < 32767 && dh < 32767 && dw < 32767, "cv2.remap requires all dimensions < 32767");
+    MA_HIP(hipSetDevice(ctx->device));
+    MA_TRY(ensure_tables(ctx));
+    MaProfScope ps(ctx, MA_K_OTHER, (double)dh * dw);
+    const dim3 grid((dw + 255) / 256, dh), block(256);
+    const float2* map = (const float2*)map_xy;
+#define MA_RI(T, M, CN) hipLaunchKernelGGL((remap_interp_kernel<T, M, CN>), grid, block, 0, ctx->stream, (const T*)src, sh, sw, map, dh, dw, (T*)dst)
+#define MA_RI_CN(T, M) do { if (cn == 1) MA_RI(T, M, 1); else if (cn == 2) MA_RI(T, M, 2); else if (cn == 3) MA_RI(T, M, 3); else MA_RI(T, M, 4); } while (0)
+#define MA_RI_T(T) do { if (interp == MA_INTER_NEAREST) MA_RI_CN(T, MA_INTER_NEAREST); else if (interp == MA_INTER_CUBIC) MA_RI_CN(T, MA_INTER_CUBIC); \
+                        else MA_RI_CN(T, MA_INTER_LANCZOS4); } while (0)
+    if (dtype == MA_U8) MA_RI_T(uint8_t);
+    else if (dtype == MA_U16) MA_RI_T(uint16_t);
+    else MA_RI_T(float);
+#undef MA_RI_T
+#undef MA_RI_CN
+#undef MA_RI
+    MA_HIP(hipGetLastError());
+    return MA_OK;
+}
+
+int ma_warp_tiled_interp(ma_ctx* ctx, const void* img, int dtype, int H, int W, const float* flow, int tile, int overlap,
+                         void* out, int interp)
+{
+    MA_REQUIRE(interp_known(interp), "interp must be MA_INTER_NEAREST, _LINEAR, _CUBIC or _LANCZOS4");
+    if (interp == MA_INTER_LINEAR) return ma_warp_tiled(ctx, img, dtype, H, W, flow, tile, overlap, out);
+    MA_REQUIRE(ctx && img && flow && out, "NULL argument");
+    MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
+    MA_REQUIRE(H > 0 && W > 0, "bad image size");
+    MA_REQUIRE(tile >= 0 && overlap >= 0, "tile/overlap must be >= 0");
+    const MaTiling g = ma_make_tiling(H, W, tile, overlap);
+    MA_REQUIRE(g.Ph < 32767 && g.Pw < 32767, "cv2.remap requires window dimensions < 32767");
+    MA_HIP(hipSetDevice(ctx->device));
+    MA_TRY(ensure_tables(ctx));
+    MaProfScope ps(ctx, MA_K_OTHER, (double)H * W);
+    return launch_warp(ctx, img, dtype, g, (const float2*)flow, out, 0, H, interp);
+}
+
+// Page-warp driver with the interpolation modes: ma_warp_pages_host's pipeline, built from ma_warp_pages_plan, the engine
+// and event calls.  An upload thread copies band after band of page i into input slot i % NS on the H2D engine, this
+// thread launches each band's warp on the compute engine once its source rows are in, a download thread copies the band's
+// output rows out on the D2H engine; events order the engines, counters under one mutex order the threads.
+int ma_warp_pages_host_interp(ma_ctx* ctx, const void* const* pages_host, void* const* out_host, int n_pages, int dtype,
+                              int H, int W, const float* flow, int tile, int overlap, int interp)
+{
+    MA_REQUIRE(interp_known(interp), "interp must be MA_INTER_NEAREST, _LINEAR, _CUBIC or _LANCZOS4");
+    if (interp == MA_INTER_LINEAR) return ma_warp_pages_host(ctx, pages_host, out_host, n_pages, dtype, H, W, flow, tile, overlap);
+    MA_REQUIRE(ctx && pages_host && out_host && flow, "NULL argument");
+    MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
+    MA_REQUIRE(n_pages >= 0, "bad page count");
+    long long band_bytes = 0;
+    MA_TRY(ma_ctx_get_option(ctx, MA_OPT_WARP_BAND_BYTES, &band_bytes));
+    int band_rows = H, nband = 1;
+    MA_TRY(ma_warp_pages_plan(dtype, H, W, tile, overlap, (size_t)band_bytes, &band_rows, &nband));
+    const MaTiling g = ma_make_tiling(H, W, tile, overlap);
+    MA_REQUIRE(g.Ph < 32767 && g.Pw < 32767, "cv2.remap requires window dimensions < 32767");
+    for (int i = 0; i < n_pages; i++) MA_REQUIRE(pages_host[i] && out_host[i], "NULL page pointer");
+    if (n_pages == 0) return MA_OK;
+    MA_HIP(hipSetDevice(ctx->device));
+    MA_TRY(ensure_tables(ctx));
+
+    constexpr int NS = 3;
+    const int ns = n_pages < NS ? n_pages : NS;
+    const size_t rowb = (size_t)W * ma_esize(dtype), nb = (size_t)H * rowb, bytes = ma_align_up(nb, 256);
+    MA_TRY(ma_ws_reserve(ctx, bytes * 2 * ns));   // device slots in the context workspace
+    char *din[NS], *dout[NS];
+    for (int k = 0; k < ns; k++) {
+        din[k] = (char*)ctx->ws + bytes * (2 * k);
+        dout[k] = (char*)ctx->ws + bytes * (2 * k + 1);
+    }
+    std::vector<void*> ev_up((size_t)ns * nband, nullptr), ev_k((size_t)ns * nband, nullptr);
+    void* ws_idle = nullptr;
+    auto cleanup = [&]() {
+        for (void* e : ev_up) if (e) (void)ma_event_destroy(ctx, e);
+        for (void* e : ev_k) if (e) (void)ma_event_destroy(ctx, e);
+        if (ws_idle) (void)ma_event_destroy(ctx, ws_idle);
+    };
+    int rc = ma_event_create(ctx, &ws_idle);
+    for (size_t e = 0; rc == MA_OK && e < ev_up.size(); e++) {
+        rc = ma_event_create(ctx, &ev_up[e]);
+        if (rc == MA_OK) rc = ma_event_create(ctx, &ev_k[e]);
+    }
+    // the slots may still be in use by kernels enqueued earlier on the compute stream: both transfer engines start behind
+    // everything it holds now
+    if (rc == MA_OK) rc = ma_engine_record(ctx, MA_ENGINE_COMPUTE, ws_idle);
+    if (rc == MA_OK) rc = ma_engine_wait(ctx, MA_ENGINE_H2D, ws_idle);
+    if (rc == MA_OK) rc = ma_engine_wait(ctx, MA_ENGINE_D2H, ws_idle);
+    if (rc != MA_OK) {
+        cleanup();
+        return rc;
+    }
+    // output rows of band b, and the source rows that must be resident before it runs
+    auto band_begin = [&](int b) { return b * band_rows; };
+    auto band_end = [&](int b) { return std::min(H, (b + 1) * band_rows); };
+    auto src_end = [&](int b) { return b == nband - 1 ? H : std::min(H, (b + 1) * band_rows + g.ov); };
+
+    std::mutex mu;
+    std::condition_variable cv;
+    long long uploaded = 0, launched = 0;   // in units (page * nband + band)
+    int downloaded = 0;                     // in pages
+    int failed = MA_OK;
+    std::string what;
+    auto fail = [&](int r) {   // called with mu held
+        if (failed == MA_OK) { failed = r; what = ma_last_error(); }
+        cv.notify_all();
+    };
+    // byte offsets at which the bands end: in the source (a band's window reaches `overlap` rows further) and in the result.
+    // A page is ONE copy per direction in pieces (ma_engine_*_pieces): the staging of pageable memory keeps its chunks in
+    // flight across the band boundaries, the bands only decide where the events are recorded and waited for.
+    std::vector<size_t> cuts_src(nband), cuts_out(nband);
+    for (int b = 0; b < nband; b++) {
+        cuts_src[b] = (size_t)src_end(b) * rowb;
+        cuts_out[b] = (size_t)band_end(b) * rowb;
+    }
+    std::thread up([&]() {
+        for (int i = 0; i < n_pages; i++) {
+            const int k = i % ns;
+            {   // slot k is free again once page i - ns has been downloaded
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return failed != MA_OK || downloaded > i - ns; });
+                if (failed != MA_OK) return;
+            }
+            const int r = ma_engine_h2d_pieces(ctx, MA_ENGINE_H2D, din[k], pages_host[i], nb, cuts_src.data(), nband, [&](int b) {
+                const int rr = ma_engine_record(ctx, MA_ENGINE_H2D, ev_up[(size_t)k * nband + b]);
+                std::lock_guard<std::mutex> lk(mu);
+                if (rr != MA_OK) return rr;
+                if (failed != MA_OK) return failed;
+                uploaded = (long long)i * nband + b + 1;
+                cv.notify_all();
+                return (int)MA_OK;
+            }, false);   // no wait at the page boundary: the next page's first chunk is staged under this page's last DMAs
+            if (r != MA_OK) {
+                std::lock_guard<std::mutex> lk(mu);
+                fail(r);
+                return;
+            }
+        }
+        const int r = ma_engine_sync(ctx, MA_ENGINE_H2D);
+        if (r != MA_OK) {
+            std::lock_guard<std::mutex> lk(mu);
+            fail(r);
+        }
+    });
+    std::thread down([&]() {
+        for (int i = 0; i < n_pages; i++) {
+            const int k = i % ns;
+            const int r = ma_engine_d2h_pieces(ctx, MA_ENGINE_D2H, out_host[i], dout[k], nb, cuts_out.data(), nband, [&](int b) {
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return failed != MA_OK || launched > (long long)i * nband + b; });
+                    if (failed != MA_OK) return failed;
+                }
+                return ma_engine_wait(ctx, MA_ENGINE_D2H, ev_k[(size_t)k * nband + b]);
+            });
+            std::lock_guard<std::mutex> lk(mu);
+            if (r != MA_OK) { fail(r); return; }
+            downloaded = i + 1;
+            cv.notify_all();
+        }
+    });
+    const long long n_units = (long long)n_pages * nband;
+    for (long long u = 0; u < n_units; u++) {
+        const int i = (int)(u / nband), b = (int)(u % nband), k = i % ns;
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return failed != MA_OK || uploaded > u; });
+            if (failed != MA_OK) break;
+        }
+        int r = ma_engine_wait(ctx, MA_ENGINE_COMPUTE, ev_up[(size_t)k * nband + b]);
+        if (r == MA_OK) r = launch_warp(ctx, din[k], dtype, g, (const float2*)flow, dout[k], band_begin(b), band_end(b), interp);
+        if (r == MA_OK) r = ma_engine_record(ctx, MA_ENGINE_COMPUTE, ev_k[(size_t)k * nband + b]);
+        std::lock_guard<std::mutex> lk(mu);
+        if (r != MA_OK) { fail(r); break; }
+        launched = u + 1;
+        cv.notify_all();
+    }
+    up.join();
+    down.join();
+    // also when a thread gave up early: nothing of this call may still be reading the caller's pages or writing its
+    // results once it has returned
+    (void)ma_engine_sync(ctx, MA_ENGINE_H2D);
+    (void)ma_engine_sync(ctx, MA_ENGINE_D2H);
+    (void)hipStreamSynchronize(ctx->stream);
+    cleanup();
+    if (failed != MA_OK) {
+        ma_set_error("%s", what.c_str());
+        return failed;
+    }
+    return MA_OK;
+}
+
+} // extern "C"

@@ -25,6 +25,20 @@ def _dt(dtype):
     return _DT[dtype]
 
 
+INTERPOLATIONS = {"nearest": L.MA_INTER_NEAREST, "linear": L.MA_INTER_LINEAR, "cubic": L.MA_INTER_CUBIC,
+                  "lanczos4": L.MA_INTER_LANCZOS4}
+
+
+def interp_code(mode):
+    """cv2's interpolation code of a mode given by name ("nearest", "linear", "cubic", "lanczos4") or by that code
+    (0, 1, 2, 4); ValueError for anything else."""
+    if isinstance(mode, str) and mode in INTERPOLATIONS:
+        return INTERPOLATIONS[mode]
+    if isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and int(mode) in INTERPOLATIONS.values():
+        return int(mode)
+    raise ValueError(f"unknown interpolation {mode!r}: expected one of {sorted(INTERPOLATIONS)} or cv2's codes 0, 1, 2, 4")
+
+
 class DeviceArray:
     """Dense row-major array living in HBM.  Freed back to the context's pool on `free()`/GC."""
 
@@ -589,25 +603,39 @@ class Context:
                   nrep_max, C.byref(n))
         return flow, [(r.factor, (r.h, r.w), r.mi_after, r.mi_before, bool(r.accepted)) for r in reps[:n.value]]
 
-    def remap(self, src, map_xy):
-        """cv2.remap(src, map_xy, None, INTER_LINEAR)."""
+    def remap(self, src, map_xy, interpolation="linear"):
+        """cv2.remap(src, map_xy, None, interpolation): "nearest", "linear", "cubic", "lanczos4" or cv2's codes 0, 1, 2, 4
+        (include/microaligner_interp.h)."""
+        interp = interp_code(interpolation)
         cn = 1 if src.ndim == 2 else src.shape[2]
         sh, sw = src.shape[:2]
         dh, dw = map_xy.shape[:2]
         if map_xy.dtype != np.float32 or map_xy.ndim != 3 or map_xy.shape[2] != 2:
             raise ValueError("map must be (h, w, 2) float32")
         dst = self.empty((dh, dw) if src.ndim == 2 else (dh, dw, cn), src.dtype)
-        self._run(self.lib.ma_remap_bilinear, src.ptr, _dt(src.dtype), cn, sh, sw, map_xy.ptr, dh, dw,
-                                           dst.ptr)
+        if interp == L.MA_INTER_LINEAR:
+            self._run(self.lib.ma_remap_bilinear, src.ptr, _dt(src.dtype), cn, sh, sw, map_xy.ptr, dh, dw,
+                                               dst.ptr)
+        else:
+            self._run(self.lib.ma_remap_interp, src.ptr, _dt(src.dtype), cn, sh, sw, map_xy.ptr, dh, dw, dst.ptr, interp)
         return dst
 
-    def warp(self, img, flow, tile, overlap, minmax=False, flow_cells=False):
+    def warp(self, img, flow, tile, overlap, minmax=False, flow_cells=False, interpolation="linear"):
         """Warper.warp() (warper.py:37-53).  minmax=True also leaves the output's (min, max) on the device
         (out.minmax) for a following dog_u8; flow_cells=True the per-cell maxima of `flow` (flow.cellkeys) for a
-        following merge_flows (only where the tiling has cells: tile > 2*overlap > 0)."""
+        following merge_flows (only where the tiling has cells: tile > 2*overlap > 0).  interpolation: as remap(); the
+        by-products belong to the linear warp of register() and are not offered with the other modes."""
+        interp = interp_code(interpolation)
         H, W = img.shape
         if flow.shape != (H, W, 2) or flow.dtype != np.float32:
             raise ValueError(f"flow must be float32 of shape {(H, W, 2)}, got {flow.dtype} {flow.shape}")
+        if interp != L.MA_INTER_LINEAR:
+            if minmax or flow_cells:
+                raise ValueError("minmax / flow_cells are by-products of the linear warp only")
+            out = self.empty((H, W), img.dtype)
+            self._run(self.lib.ma_warp_tiled_interp, img.ptr, _dt(img.dtype), H, W, flow.ptr, int(tile), int(overlap),
+                      out.ptr, interp)
+            return out
         out = self.empty((H, W), img.dtype)
         if flow_cells and tile > 2 * overlap > 0:
             ncell = (2 * -(-W // tile) + 1) * (2 * -(-H // tile) + 1)
@@ -627,10 +655,11 @@ class Context:
                                            int(overlap), out.ptr)
         return out
 
-    def warp_pages(self, pages, flow, tile, overlap, out=None):
+    def warp_pages(self, pages, flow, tile, overlap, out=None, interpolation="linear"):
         """warp_and_save_pages (__main__.py:288-302): warp every HOST page with one device-resident flow.
         pages: sequence of equal-shape C-contiguous numpy arrays; out: optional sequence of writable arrays of the
-        same shape/dtype (e.g. memmap rows), allocated if None.  Returns `out`."""
+        same shape/dtype (e.g. memmap rows), allocated if None; interpolation: as remap().  Returns `out`."""
+        interp = interp_code(interpolation)
         pages = [np.ascontiguousarray(p) for p in pages]
         if not pages:
             return []
@@ -650,7 +679,10 @@ class Context:
         n = len(pages)
         src = (C.c_void_p * n)(*[p.ctypes.data for p in pages])
         dst = (C.c_void_p * n)(*[o.ctypes.data for o in out])
-        self._run(self.lib.ma_warp_pages_host, src, dst, n, dt, H, W, flow.ptr, int(tile), int(overlap))
+        if interp == L.MA_INTER_LINEAR:
+            self._run(self.lib.ma_warp_pages_host, src, dst, n, dt, H, W, flow.ptr, int(tile), int(overlap))
+        else:
+            self._run(self.lib.ma_warp_pages_host_interp, src, dst, n, dt, H, W, flow.ptr, int(tile), int(overlap), interp)
         return out
 
     def merge_flows(self, flow1, flow2, tile, overlap):

@@ -1,12 +1,20 @@
-"""Tiled backward-bilinear warp (counterpart of microaligner/optflow_reg/warper.py:29-76).
+"""Tiled backward warp (counterpart of microaligner/optflow_reg/warper.py:29-76).
 
 One HIP kernel evaluates, per output pixel, the window the reference would have cut
 (tile_size + 2*overlap, zero padded), the window-local map float32(x_local - flow) and the
-cv2.remap INTER_LINEAR arithmetic (fixed point for uint8, float for uint16/float32).
+cv2.remap arithmetic of `interpolation`: INTER_LINEAR by default, as the reference calls it (fixed point
+for uint8, float for uint16/float32), or INTER_NEAREST / INTER_CUBIC / INTER_LANCZOS4
+(include/microaligner_interp.h).
 """
 import numpy as np
 
-from ..device import DeviceArray, get_context
+from .._lib import MA_INTER_LINEAR as INTER_LINEAR
+from ..device import DeviceArray, get_context, interp_code
+
+
+def _mode(interp):
+    """keyword arguments of the Context calls: none for the default linear mode, whose calls stay exactly as they were"""
+    return {} if interp == INTER_LINEAR else {"interpolation": interp}
 
 
 class Warper:
@@ -17,12 +25,15 @@ class Warper:
         self.flow = np.array([])
         self.tile_size = 1000
         self.overlap = 100
+        # "nearest", "linear", "cubic", "lanczos4" or cv2's codes 0, 1, 2, 4; checked before any device work
+        self.interpolation = "linear"
 
     def warp(self):
         if len(self.image) == 0:
             raise ValueError("No image provided")
         if len(self.flow) == 0:
             raise ValueError("No flow provided")
+        interp = interp_code(self.interpolation)
         ctx = get_context()
         like = self.image
         if np.ndim(like) != 2:
@@ -35,12 +46,12 @@ class Warper:
             # kernel and download of the one page overlap
             flow = ctx.asdevice(self.flow)
             out = ctx.host_empty(like.shape, like.dtype)
-            ctx.warp_pages([like], flow, self.tile_size, self.overlap, [out])
+            ctx.warp_pages([like], flow, self.tile_size, self.overlap, [out], **_mode(interp))
             self.image = np.array([])
             self.flow = np.array([])
             return out
         img, flow = ctx.asdevice(like), ctx.asdevice(self.flow)
-        out = ctx.warp(img, flow, self.tile_size, self.overlap)
+        out = ctx.warp(img, flow, self.tile_size, self.overlap, **_mode(interp))
         # like the reference (warper.py:41,45) the inputs are consumed
         self.image = np.array([])
         self.flow = np.array([])
@@ -51,7 +62,8 @@ class Warper:
         flow uploaded once and the page transfers overlapped.  Unlike warp() this keeps `self.flow`."""
         if len(self.flow) == 0:
             raise ValueError("No flow provided")
+        interp = interp_code(self.interpolation)
         ctx = get_context()
         flow = ctx.asdevice(self.flow)
         self.flow = flow  # stays resident for further calls
-        return ctx.warp_pages(pages, flow, self.tile_size, self.overlap, out)
+        return ctx.warp_pages(pages, flow, self.tile_size, self.overlap, out, **_mode(interp))
