@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: OptFlowRegistrator.register() + one Warper.warp(mov, flow).
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg2|cfg4|cfg5|cfg1]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg2|cfg4|cfg5|cfg1] [--full]
 
 A step is one registration + warp of one synthetic (ref, mov) pair that is already resident in HBM.
 Every rank (one process per GPU) works on its own pair -- independent units, no data-path collective
  -- so scaling is weak and `value` = N * H*W / max-over-ranks time.  The control plane
 (barrier, max of the per-rank times) uses torch.distributed/gloo on the host; the GPU is driven only by
 libmicroaligner_hip.so.  Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, K timed steps, --dump-outputs if
+given, and the JSON line (headline, per-rank rows, the per-kernel times the timed steps themselves recorded).  --full adds
+everything that is measured or checked beside it: the shader clock probe and the roofline entries priced with it, the
+informational `variants` legs (numpy in/out, FMA rounding models, page warps, several pairs in flight), the CPU baseline
+and, at N > 1, the shared-array results leg and the numpy -> numpy `host_modes`.
 
 Launching: under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` every process is a
 rank (RANK / LOCAL_RANK / WORLD_SIZE from the environment).  Started directly with `--gpus N` (N > 1) and no
@@ -981,9 +987,13 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "u8"], help="input dtype (u8: the pipeline-faithful cfg4 variant)")
     ap.add_argument("--fused", action="store_true", help="window blur with FMA (MA_FB_MULADD_FUSED)")
     ap.add_argument("--dog-fused", action="store_true", help="dog() chain with FMA (MA_DOG_FUSED_BLUR | MA_DOG_FUSED_SCALE)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything beside it: clock probe and roofline, the "
+                         "informational legs (`variants`), the CPU baseline, at N > 1 the shared-array results leg and the "
+                         "host modes.  Off: the run does only what the headline needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-dog", action="store_true", help="experiment: run the workload with use_dog=False")
-    ap.add_argument("--no-variants", action="store_true", help="skip the informational legs (profiling runs)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the informational legs")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="edge of the CPU-baseline sample; 0: the full workload on hosts with >= 128 hardware threads "
                          "(the 16384^2 oracle run takes ~45 s there), else 4096")
@@ -994,7 +1004,7 @@ def main():
                     help="uint16 pages of the informational page-warp leg (SURVEY 8f-1: Warper.warp_pages and the per-page "
                          "Warper.warp() loop, numpy in -> numpy out; 0: skip)")
     ap.add_argument("--no-shared-results", action="store_true",
-                    help="N > 1: skip writing every rank's last flow / warped image into the node-wide shared array")
+                    help="N > 1 with --full: skip writing every rank's last flow / warped image into the node-wide shared array")
     ap.add_argument("--no-companion", action="store_true",
                     help="MA_OPT_COMPANION_STREAM = 0: every kernel alone on the chip (per-kernel timings comparable from "
                          "run to run; the step is ~3 ms longer)")
@@ -1009,8 +1019,8 @@ def main():
     ap.add_argument("--host-modes", default="auto", choices=["auto", "on", "off"],
                     help="after the timed loop every rank runs the numpy -> numpy modes (parallel.stream_pairs and "
                          "Warper.warp_pages, pageable and page-locked buffers) at the same time and the line reports them per "
-                         "rank with the whole-node rates (`host_modes`); auto: when N > 1 -- the modes that can fail to "
-                         "scale -- at N = 1 the `variants` legs cover them")
+                         "rank with the whole-node rates (`host_modes`); auto: with --full when N > 1 -- the modes that can "
+                         "fail to scale -- at N = 1 the `variants` legs cover them")
     ap.add_argument("--host-mode-pairs", type=int, default=8, help="pairs per rank of the stream_pairs host modes")
     ap.add_argument("--recompute-rounds", action="store_true",
                     help="cfg5 --feature-init: FeatureRegistrator recomputes a round that follows a rejected one (default: replayed)")
@@ -1061,6 +1071,8 @@ def main():
     # the pairs of this rank: its own pair (weak scaling), or its share of K pairs dealt round-robin (strong scaling)
     my_pairs = list(range(rank, args.pairs_total, world)) if args.pairs_total else [rank]
     pairs_per_step = args.pairs_total or world
+    # the numpy -> numpy host modes: asked for by name, or part of a --full run at N > 1
+    want_modes = args.host_modes == "on" or (args.host_modes == "auto" and args.full and world > 1)
 
     def reduce_max(x):
         if dist is None:
@@ -1096,7 +1108,6 @@ def main():
         shared_ok = bool(all(np.all(store[i] == 1000 * (i % world) + i) for i in range(n_units)))
         row = {"rank": rank, "ms_per_step": mine / args.steps * 1e3, "pairs": my_pairs,
                "device": None, "pci_bus_id": None, "units_loaded": sorted(loaded)}
-        want_modes = args.host_modes == "on" or (args.host_modes == "auto" and world > 1)
         rows = rank_table(dist, world, rank, row)
         host_rows_all = None
         if want_modes:       # the plumbing of the host-mode rows (soft barriers, row exchange, report) with made-up times
@@ -1180,8 +1191,8 @@ def main():
         else:
             ref, mov = synthetic.make_pair(H, W, seed=1 + idx, dtype=np_dtype)
         work.append((ctx.asdevice(ref), ctx.asdevice(mov), inv_affine, host))
-    keep_host = world == 1 and not args.no_variants and not args.pairs_total
-    want_modes = (args.host_modes == "on" or (args.host_modes == "auto" and world > 1)) and not wl.get("affine")
+    keep_host = args.full and world == 1 and not args.no_variants and not args.pairs_total
+    want_modes = want_modes and not wl.get("affine")
     if not keep_host and freg is None and not want_modes:
         ref = mov = None
     ctx.forget_host_arrays()
@@ -1245,8 +1256,8 @@ def main():
     barrier()
     ctx.profile(False)
     elapsed = reduce_max(t1 - t0)
-    # the shader clock the chip holds under the blur kernels' instruction mix, while it is still hot
-    clock_ghz = ctx.clock_probe(20.0)
+    # --full: the shader clock the chip holds under the blur kernels' instruction mix, while it is still hot
+    clock_ghz = ctx.clock_probe(20.0) if args.full else None
     # results of the sharded job come back to rank 0 over gloo (host side), timed apart from the device time: per pair a
     # checksum of the flow and of the warped image (the arrays themselves stay where the next pipeline stage needs them)
     tg0 = time.perf_counter()
@@ -1256,14 +1267,16 @@ def main():
         summary = {"pair": my_pairs[-1] if my_pairs else None, "flow_minmax": [float(v) for v in ctx.minmax(flow)],
                    "warped_minmax": [float(v) for v in ctx.minmax(warped)]}
     info = device_info(dev_index)
+    row = {"rank": rank, "device": dev_index, "pci_bus_id": info["pci_bus_id"], "name": info["name"],
+           "hbm_free_gb": round(info["mem_free"] / 2 ** 30, 1), "hbm_total_gb": round(info["mem_total"] / 2 ** 30, 1),
+           "cpus": (f"{cpu_ranges(bound_cpus)} ({len(bound_cpus)} of {len(all_cpus)}, local to the device)"
+                    if bound_cpus else f"all {len(all_cpus)} (no NUMA binding: topology unknown or single node)"),
+           "pairs": my_pairs, "ms_per_step": round((t1 - t0) / args.steps * 1e3, 3)}
+    if clock_ghz is not None:
+        row["clock_ghz"] = round(clock_ghz, 3)
+    row["result"] = summary
     # the headline's rows are gathered BEFORE the host modes: nothing that happens in those can cost the line any more
-    rows = rank_table(dist, world, rank, {
-        "rank": rank, "device": dev_index, "pci_bus_id": info["pci_bus_id"], "name": info["name"],
-        "hbm_free_gb": round(info["mem_free"] / 2 ** 30, 1), "hbm_total_gb": round(info["mem_total"] / 2 ** 30, 1),
-        "cpus": (f"{cpu_ranges(bound_cpus)} ({len(bound_cpus)} of {len(all_cpus)}, local to the device)"
-                 if bound_cpus else f"all {len(all_cpus)} (no NUMA binding: topology unknown or single node)"),
-        "pairs": my_pairs, "ms_per_step": round((t1 - t0) / args.steps * 1e3, 3), "clock_ghz": round(clock_ghz, 3),
-        "result": summary})
+    rows = rank_table(dist, world, rank, row)
     gather_ms = (time.perf_counter() - tg0) * 1e3
     dumped = None
     if args.dump_outputs and rank == 0 and out is not None:
@@ -1280,7 +1293,7 @@ def main():
     # collective after the one broadcast of rank 0's decisions: barriers and rows go through SoftSync, every wait bounded.
     host_rows_all, host_skip, shared_ms, shared_note, soft = None, None, None, None, None
     all_have_results = reduce_max(0.0 if out is not None else 1.0) < 0.5     # (--pairs-total below N leaves ranks without a pair)
-    want_shared = world > 1 and all_have_results and not args.no_shared_results
+    want_shared = args.full and world > 1 and all_have_results and not args.no_shared_results
     want_modes = want_modes and all_have_results
     plan = [None, None, 0]           # why the shared-results leg is skipped, why the host modes are, the store's port
     if rank == 0 and want_shared:
@@ -1302,10 +1315,11 @@ def main():
         if rank == 0:
             plan[2] = free_port()
         dist.broadcast_object_list(plan, src=0)        # the last collective before the line
-        try:
-            soft = soft_sync(dist, world, rank, args.host_mode_timeout, plan[2])
-        except Exception as e:   # noqa: BLE001
-            print(f"bench.py: rank {rank}: store of the informational legs: {e!r}", file=sys.stderr)
+        if want_shared or want_modes:                  # (the same decision on every rank: arguments and a reduction)
+            try:
+                soft = soft_sync(dist, world, rank, args.host_mode_timeout, plan[2])
+            except Exception as e:   # noqa: BLE001
+                print(f"bench.py: rank {rank}: store of the informational legs: {e!r}", file=sys.stderr)
     # the data plane of a multi-rank job: each rank's download engine writes its (last) flow and warped image straight into
     # a node-wide shared array (parallel.shared_array; the reference writes pages into its memmapped output,
     # __main__.py:116-132) -- nothing but reports crosses the control plane
@@ -1349,10 +1363,13 @@ def main():
         fb_esz = 1 if reg.use_dog else esz
         pristine = (not args.size and not args.fused and not args.dog_fused and not args.no_dog and args.dtype == "f32"
                     and not args.pairs_total and not args.feature_init)
-        tps, tsrc, tnote = pmc_traffic(args.workload) if pristine else ({}, None, "not the profiled command line")
+        if args.full:
+            tps, tsrc, tnote = pmc_traffic(args.workload) if pristine else ({}, None, "not the profiled command line")
+            kclk, kclk_src = kernel_clocks(args.workload) if pristine else ({}, None)
+        else:   # a plain run prints the compact `kernels` rows only: they need neither the PMC traffic nor any clock
+            tps, tsrc, tnote, kclk, kclk_src = {}, None, None, {}, None
         win = reg.overlap - (1 - reg.overlap % 2)
         nsteps_prof = args.steps * max(1, len(work))
-        kclk, kclk_src = kernel_clocks(args.workload) if pristine else ({}, None)
         kernels = {k: roofline_entry(k, v, iters, fb_esz if k == "polyexp_m0" else esz, nsteps_prof, tps, win // 2, tsrc,
                                      clock_ghz, args.fused if k != "dog" else args.dog_fused, tnote, kclk.get(k), kclk_src)
                    for k, v in prof.items()}
@@ -1381,8 +1398,9 @@ def main():
                                           if freg is not None else None),
                        "parallelism": f"{pairs_per_step} independent pairs per step dealt round-robin to {world} rank(s), "
                                       f"one rank per GPU, {min(world, ndev)} GPU(s), no collective on the data path"},
-            # one compact row per kernel group; the full entries of the dominant kernel (`roofline`), the north-star kernel
-            # (`roofline_polyexp`) and the vertical pass (`roofline_blur_v`) close the line, where a tail reader sees them
+            # one compact row per kernel group, from the timed steps' own launch events; with --full the full entries of the
+            # dominant kernel (`roofline`), the north-star kernel (`roofline_polyexp`) and the vertical pass (`roofline_blur_v`)
+            # close the line, where a tail reader sees them
             "kernels": {k: {f: v[f] for f in ("bound", "achieved", "peak", "unit", "frac", "avg_launch_ms", "launches",
                                               "share_of_kernel_time", "px_per_launch") if f in v}
                         for k, v in kernels.items()},
@@ -1392,14 +1410,15 @@ def main():
                                 "loop (register.hip), so the sum exceeds the step and launches that share the chip are "
                                 "longer than they would be alone",
             "step_ms_host": step_ms_host,
-            "sustained_clock_ghz": round(clock_ghz, 3),
             "library": ctx.lib.ma_version().decode(),
             "ranks": rows,
             "rank_ms_per_step": {"min": min(per), "mean": round(sum(per) / len(per), 3), "max": max(per)},
             "gather_ms": round(gather_ms, 3),
-            "results_to_shared_array_ms": round(shared_ms, 1) if shared_ms is not None else None,
-            "results_to_shared_array": shared_note,
         }
+        if args.full:
+            res["sustained_clock_ghz"] = round(clock_ghz, 3)
+            res["results_to_shared_array_ms"] = round(shared_ms, 1) if shared_ms is not None else None
+            res["results_to_shared_array"] = shared_note
         if dumped is not None:
             res["dump_outputs"] = dumped
         if host_skip:
@@ -1484,7 +1503,7 @@ def main():
                 informational(V, "page_warp", lambda: page_warp_leg(args.page_warps, H, W, reg.tile_size, reg.overlap))
             if args.lanes > 1 and inv_affine is None:
                 informational(V, f"lanes{args.lanes}", leg_lanes)
-        if world == 1 and freg is not None and not args.no_variants and freg.skip_repeated_rounds:
+        if args.full and world == 1 and freg is not None and not args.no_variants and freg.skip_repeated_rounds:
             def leg_rounds_recomputed():
                 # the same tiles with every round of FeatureRegistrator recomputed, as the reference does (a round after a
                 # rejected one sees the same images and finds the same answer; the default replays it)
@@ -1502,7 +1521,7 @@ def main():
                 return {"ms_per_tile": round(tr * 1e3, 3), "what": "FeatureRegistrator.skip_repeated_rounds = False: repeated rounds "
                         "recomputed instead of replayed; same matrices (tests/test_feature_reg.py::test_replayed_rounds_equal_recomputed_rounds)"}
             informational(res.setdefault("variants", {}), "feature_rounds_recomputed", leg_rounds_recomputed)
-        if world == 1 and wl.get("affine") and not args.no_variants and args.lanes > 1 and len(work) > 1:
+        if args.full and world == 1 and wl.get("affine") and not args.no_variants and args.lanes > 1 and len(work) > 1:
             def leg_tile_lanes():
                 tl, n = tile_lanes_leg(args.lanes, args.steps, ctx.device, work, params, freg is not None,
                                         freg.skip_repeated_rounds if freg is not None else True)
@@ -1511,18 +1530,19 @@ def main():
                                 "and host thread each): what parallel.align_pairs(lanes=...) does; the headline runs them one "
                                 "after the other"}
             informational(res.setdefault("variants", {}), f"tile_lanes{args.lanes}", leg_tile_lanes)
-        if world == 1 and not args.no_cpu_baseline and not args.pairs_total:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.pairs_total:
             set_affinity(all_cpus)      # the CPU baseline uses every core of the host, not just the GPU's node
             # a bounded sample: the full workload where >= 128 CPUs can really run, else 8192^2 (the GPU boxes of this pool grant
             # 16 CPUs of time: ~9 s there; the full 16384^2 pair would take most of a minute)
             sample = args.cpu_sample or (H if effective_cpus()[0] >= 128 else 8192)
             informational(res, "cpu_baseline", lambda: cpu_baseline(min(sample, H), params))
-        for key, name in (("roofline_blur_v", "blur_v"), ("roofline_polyexp", "polyexp_m0")):
-            if name != dominant:
-                res[key] = kernels.get(name)
-        if dominant != "blur_h_solve":
-            res["roofline_blur_h_solve"] = kernels.get("blur_h_solve")
-        res["roofline"] = kernels.get(dominant)
+        if args.full:
+            for key, name in (("roofline_blur_v", "blur_v"), ("roofline_polyexp", "polyexp_m0")):
+                if name != dominant:
+                    res[key] = kernels.get(name)
+            if dominant != "blur_h_solve":
+                res["roofline_blur_h_solve"] = kernels.get("blur_h_solve")
+            res["roofline"] = kernels.get(dominant)
         print(json.dumps(res))
     finish(dist, rank)
 

@@ -51,7 +51,7 @@ def test_bench_gpus_n_launches_its_own_ranks():
     launch / barrier / max-reduce / JSON plumbing is testable here."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--dry-run"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+                        "--dry-run", "--full"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -68,7 +68,7 @@ def test_bench_eight_ranks_report_per_rank_rows_and_deal_pairs_round_robin():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "0",
-                        "--dry-run", "--workload", "cfg5", "--pairs-total", "64"], capture_output=True, text=True,
+                        "--dry-run", "--full", "--workload", "cfg5", "--pairs-total", "64"], capture_output=True, text=True,
                        timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -82,8 +82,8 @@ def test_bench_eight_ranks_report_per_rank_rows_and_deal_pairs_round_robin():
     per = [row["ms_per_step"] for row in res["ranks"]]
     assert res["rank_ms_per_step"] == {"min": min(per), "mean": sum(per) / 8, "max": max(per)}
     assert abs(res["ms_per_step"] - max(per)) < 1e-9            # the headline time is the slowest rank's
-    # the numpy -> numpy modes (the ones that can fail to scale) are part of every N > 1 line: per mode one
-    # time per rank, the whole-node rates from the slowest rank, and whether the library moved the buffers by DMA as they are
+    # the numpy -> numpy modes (the ones that can fail to scale) are part of every N > 1 --full line: per mode
+    # one time per rank, the whole-node rates from the slowest rank, and whether the library moved the buffers by DMA as they are
     hm = res["host_modes"]
     for mode in ("stream_pairs_pageable", "stream_pairs_page_locked", "warp_pages_pageable", "warp_pages_page_locked"):
         row = hm[mode]
@@ -152,7 +152,8 @@ def test_bench_line_survives_a_rank_that_fails_inside_the_host_modes():
     env["OMP_NUM_THREADS"] = "1"
     env["MA_BENCH_DRY_FAIL"] = "1:2"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "0",
-                        "--dry-run", "--host-mode-timeout", "4"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--dry-run", "--full", "--host-mode-timeout", "4"], capture_output=True, text=True, timeout=900, env=env,
+                       cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     # (no wall-clock bound here: the first `import torch` of three ranks on a cold box takes minutes by itself; a rank that waited
     # for a collective instead of the 4-second barrier would fail the content checks below -- or the process group's timeout)
