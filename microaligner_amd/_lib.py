@@ -155,6 +155,14 @@ INTERP_SIGNATURES = {
     "ma_warp_pages_host_interp": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp, _i, _i, _i]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_compose.h (one resampling through an affine
+# matrix and a flow)
+COMPOSE_SIGNATURES = {
+    "ma_warp_affine_flow": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, C.POINTER(_d), _vp, _i]),
+    "ma_warp_affine_flow_pages_host": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _vp, _i, _i,
+                                            C.POINTER(_d), _i]),
+}
+
 _lib = None
 
 
@@ -168,7 +176,8 @@ def load():
             f"{LIB_PATH} not found: build the HIP extension first (python -m microaligner_amd.build). "
             "microaligner_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + \
+            list(COMPOSE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -39,6 +39,30 @@ def interp_code(mode):
     raise ValueError(f"unknown interpolation {mode!r}: expected one of {sorted(INTERPOLATIONS)} or cv2's codes 0, 1, 2, 4")
 
 
+def affine_flow_params(img_shape, img_dtype, flow_shape, flow_dtype, tmat, interpolation="linear"):
+    """Checks and host-side arguments of the one-resampling warp through a 2x3 matrix and a flow
+    (include/microaligner_compose.h), without touching a device: (interp code, rows 0-1 of M = pinv([tmat; 0 0 1]) as 6
+    float64 -- formed as transform_img_with_tmat forms it --, pad_left, pad_top of pad_to_shape(img, flow's (H, W))).
+    ValueError for an unknown mode or dtype, a tmat that is not a finite 2x3 matrix, or an image larger than the flow."""
+    interp = interp_code(interpolation)
+    _dt(img_dtype)
+    if len(img_shape) != 2:
+        raise ValueError(f"expected a 2D grayscale image, got shape {tuple(img_shape)}")
+    if len(flow_shape) != 3 or flow_shape[2] != 2 or np.dtype(flow_dtype) != np.float32:
+        raise ValueError(f"flow must be (H, W, 2) float32, got {np.dtype(flow_dtype)} {tuple(flow_shape)}")
+    try:
+        t = np.asarray(tmat, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"tmat must be a finite 2x3 matrix: {e}") from None
+    if t.shape != (2, 3) or not np.all(np.isfinite(t)):
+        raise ValueError(f"tmat must be a finite 2x3 matrix, got shape {t.shape}")
+    (h, w), (H, W) = img_shape, flow_shape[:2]
+    if h < 1 or w < 1 or h > H or w > W:
+        raise ValueError(f"the image {(h, w)} must be non-empty and no larger than the flow {(H, W)} in either dimension")
+    m = np.linalg.pinv(np.append(t, [[0, 0, 1]], axis=0))[:2].ravel()
+    return interp, m, (W - w) // 2, (H - h) // 2
+
+
 class DeviceArray:
     """Dense row-major array living in HBM.  Freed back to the context's pool on `free()`/GC."""
 
@@ -683,6 +707,47 @@ class Context:
             self._run(self.lib.ma_warp_pages_host, src, dst, n, dt, H, W, flow.ptr, int(tile), int(overlap))
         else:
             self._run(self.lib.ma_warp_pages_host_interp, src, dst, n, dt, H, W, flow.ptr, int(tile), int(overlap), interp)
+        return out
+
+    def warp_affine_flow(self, img, flow, tmat, interpolation="linear"):
+        """One resampling of `img` (h, w) through the 2x3 matrix `tmat` and the (H, W, 2) `flow` (h <= H, w <= W):
+        cv2.remap(pad_to_shape(img, (H, W)), float32(M.(p - flow(p))), interpolation) with M = pinv([tmat; 0 0 1]), the
+        whole image at once (no tile windows), integer coordinates not saturated to 16 bits
+        (include/microaligner_compose.h).  What transform_img_with_tmat followed by Warper.warp() approximates with two
+        resamplings.  Returns a DeviceArray (H, W)."""
+        interp, m, left, top = affine_flow_params(img.shape, img.dtype, flow.shape, flow.dtype, tmat, interpolation)
+        img, flow = self.asdevice(img), self.asdevice(flow)
+        (h, w), (H, W) = img.shape, flow.shape[:2]
+        out = self.empty((H, W), img.dtype)
+        self._run(self.lib.ma_warp_affine_flow, img.ptr, _dt(img.dtype), h, w, left, top, flow.ptr, H, W,
+                  (C.c_double * 6)(*[float(v) for v in m]), out.ptr, interp)
+        return out
+
+    def warp_affine_flow_pages(self, pages, flow, tmat, out=None, interpolation="linear"):
+        """warp_affine_flow() for many HOST pages (h, w) with one device-resident flow (H, W, 2): the page-warp driver of
+        include/microaligner_compose.h uploads page i + 1 while page i is warped and downloads the results in bands.
+        out: optional sequence of writable C-contiguous (H, W) arrays (e.g. memmap rows), allocated if None.  Returns `out`."""
+        pages = [np.ascontiguousarray(p) for p in pages]
+        if not pages:
+            return []
+        interp, m, left, top = affine_flow_params(pages[0].shape, pages[0].dtype, flow.shape, flow.dtype, tmat,
+                                                  interpolation)
+        (h, w), (H, W) = pages[0].shape, flow.shape[:2]
+        if any(p.shape != (h, w) or p.dtype != pages[0].dtype for p in pages):
+            raise ValueError("all pages must have the same shape and dtype")
+        if getattr(flow, "ctx", self) is not self:
+            raise ValueError("flow belongs to another context")
+        flow = self.asdevice(flow)
+        if out is None:
+            out = [np.empty((H, W), pages[0].dtype) for _ in pages]
+        if len(out) != len(pages) or any(o.shape != (H, W) or o.dtype != pages[0].dtype or not o.flags.c_contiguous
+                                         or not o.flags.writeable for o in out):
+            raise ValueError("out must hold one writable C-contiguous array of the flow's (H, W) and the page dtype per page")
+        n = len(pages)
+        src = (C.c_void_p * n)(*[p.ctypes.data for p in pages])
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in out])
+        self._run(self.lib.ma_warp_affine_flow_pages_host, src, dst, n, _dt(pages[0].dtype), h, w, left, top, flow.ptr,
+                  H, W, (C.c_double * 6)(*[float(v) for v in m]), interp)
         return out
 
     def merge_flows(self, flow1, flow2, tile, overlap):

@@ -5,11 +5,16 @@ One HIP kernel evaluates, per output pixel, the window the reference would have 
 cv2.remap arithmetic of `interpolation`: INTER_LINEAR by default, as the reference calls it (fixed point
 for uint8, float for uint16/float32), or INTER_NEAREST / INTER_CUBIC / INTER_LANCZOS4
 (include/microaligner_interp.h).
+
+With `tmat` set to a 2x3 matrix (FeatureRegistrator.register()'s, the one transform_img_with_tmat takes) the image is
+the ORIGINAL moving image and is resampled once, through the matrix and the flow together
+(include/microaligner_compose.h): the result has the flow's shape, covers the whole image (tile_size / overlap do not
+apply) and differs from transform_img_with_tmat followed by a plain warp, which interpolates twice.
 """
 import numpy as np
 
 from .._lib import MA_INTER_LINEAR as INTER_LINEAR
-from ..device import DeviceArray, get_context, interp_code
+from ..device import DeviceArray, affine_flow_params, get_context, interp_code
 
 
 def _mode(interp):
@@ -27,6 +32,8 @@ class Warper:
         self.overlap = 100
         # "nearest", "linear", "cubic", "lanczos4" or cv2's codes 0, 1, 2, 4; checked before any device work
         self.interpolation = "linear"
+        # None, or the 2x3 affine initialisation of `image`: one resampling through it and the flow (module docstring)
+        self.tmat = None
 
     def warp(self):
         if len(self.image) == 0:
@@ -34,6 +41,8 @@ class Warper:
         if len(self.flow) == 0:
             raise ValueError("No flow provided")
         interp = interp_code(self.interpolation)
+        if self.tmat is not None:
+            return self._warp_affine_flow()
         ctx = get_context()
         like = self.image
         if np.ndim(like) != 2:
@@ -57,13 +66,49 @@ class Warper:
         self.flow = np.array([])
         return out if isinstance(like, DeviceArray) else out.numpy()
 
+    def _params(self, like):
+        """affine_flow_params of `like` against the flow and tmat: every check before any device work"""
+        if np.ndim(like) != 2:
+            raise ValueError(f"Expected 2D grayscale image, got shape {np.shape(like)}")
+        return affine_flow_params(np.shape(like), like.dtype, np.shape(self.flow), self.flow.dtype, self.tmat,
+                                  self.interpolation)
+
+    def _warp_affine_flow(self):
+        like = self.image
+        self._params(like)
+        interp, tmat = interp_code(self.interpolation), self.tmat
+        ctx = get_context()
+        if isinstance(like, np.ndarray) and like.nbytes >= self.HOST_BANDED_MIN:
+            like = np.ascontiguousarray(like)
+        if isinstance(like, np.ndarray) and like.nbytes >= self.HOST_BANDED_MIN and not ctx.is_resident(like):
+            # a large host page: the page driver uploads it whole and downloads the result in bands under the kernel
+            flow = ctx.asdevice(self.flow)
+            out = ctx.host_empty(flow.shape[:2], like.dtype)
+            ctx.warp_affine_flow_pages([like], flow, tmat, [out], interpolation=interp)
+        else:
+            out = ctx.warp_affine_flow(ctx.asdevice(like), ctx.asdevice(self.flow), tmat, interpolation=interp)
+            if not isinstance(like, DeviceArray):
+                out = out.numpy()
+        # the matrix is consumed with the image and the flow
+        self.image = np.array([])
+        self.flow = np.array([])
+        self.tmat = None
+        return out
+
     def warp_pages(self, pages, out=None):
         """Apply `self.flow` to many pages (the channel x z pages of a cycle, __main__.py:288-302,427-433) with the
-        flow uploaded once and the page transfers overlapped.  Unlike warp() this keeps `self.flow`."""
+        flow uploaded once and the page transfers overlapped.  Unlike warp() this keeps `self.flow` (and `self.tmat`:
+        with a matrix every page is resampled once through it and the flow, and `out` holds arrays of the flow's shape)."""
         if len(self.flow) == 0:
             raise ValueError("No flow provided")
         interp = interp_code(self.interpolation)
+        if self.tmat is not None:
+            pages = [np.ascontiguousarray(p) for p in pages]
+            for p in pages:
+                self._params(p)
         ctx = get_context()
         flow = ctx.asdevice(self.flow)
         self.flow = flow  # stays resident for further calls
+        if self.tmat is not None:
+            return ctx.warp_affine_flow_pages(pages, flow, self.tmat, out, interpolation=interp)
         return ctx.warp_pages(pages, flow, self.tile_size, self.overlap, out, **_mode(interp))

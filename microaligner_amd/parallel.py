@@ -713,13 +713,16 @@ def register_cycle_chain(cycles: Sequence, ref_channel_ids=None, params: Optiona
 
 
 def align_pairs(pairs: Sequence, feature_params: Optional[dict] = None, optflow_params: Optional[dict] = None,
-                gather: bool = True, lanes: int = 1, stream: Optional[bool] = None):
+                gather: bool = True, lanes: int = 1, stream: Optional[bool] = None, single_resample: bool = False):
     """Two-stage alignment of independent (ref, mov) pairs -- mosaic tiles, BASELINE cfg5 -- sharded over the ranks:
     feature-based affine initialisation (FeatureRegistrator, the pipeline's first stage, __main__.py:257-286),
     transform_img_with_tmat, then the optical-flow refinement and warp (OptFlowRegistrator + Warper, :398-433).
     Returns, per pair and in pair order on rank 0, (aligned moving image, 2x3 matrix, flow).
     stream (default: on for host pairs of equal shape when lanes == 1): the rank's share goes through stream_pairs, the
-    two stages of pair k running on the device arrays while pair k+1 is uploaded and pair k-1 downloaded."""
+    two stages of pair k running on the device arrays while pair k+1 is uploaded and pair k-1 downloaded.
+    single_resample: the aligned image is the ORIGINAL moving image resampled once through the matrix and the flow
+    (Warper.tmat, include/microaligner_compose.h) instead of the flow's warp of the affine stage's output; the matrix and
+    the flow are the same either way."""
     import numpy as np
     from . import FeatureRegistrator, OptFlowRegistrator, Warper, transform_img_with_tmat
     feature_params, optflow_params = dict(feature_params or {}), dict(optflow_params or {})
@@ -742,6 +745,8 @@ def align_pairs(pairs: Sequence, feature_params: Optional[dict] = None, optflow_
         w = Warper()
         w.tile_size, w.overlap = oreg.tile_size, oreg.overlap
         w.image, w.flow = affine, flow
+        if single_resample:
+            w.image, w.tmat = mov, t_mat
         return w.warp(), t_mat, flow
 
     def stage(ctx, dref, dmov):
@@ -764,6 +769,8 @@ def align_pairs(pairs: Sequence, feature_params: Optional[dict] = None, optflow_
             setattr(oreg, k, v)
         oreg.ref_img, oreg.mov_img = dref, affine
         flow = oreg.register()
+        if single_resample:
+            return [ctx.warp_affine_flow(dmov, flow, t_mat), flow], oreg.level_reports, t_mat
         return [ctx.warp(affine, flow, oreg.tile_size, oreg.overlap), flow], oreg.level_reports, t_mat
 
     rank, ws = world()
