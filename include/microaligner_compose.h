@@ -37,8 +37,9 @@ int ma_warp_affine_flow(ma_ctx* ctx, const void* img, int dtype, int h, int w, i
                         const float* flow, int H, int W, const double m[6], void* out, int interp);
 
 /* the same for host pages (h, w) -> host pages (H, W), one device-resident flow: page i + 1 is uploaded whole while page i
- * is warped, the output leaves in bands of MA_OPT_WARP_BAND_BYTES so that its download overlaps the kernel.
- * Synchronous. */
+ * is warped, the output leaves in bands of MA_OPT_WARP_BAND_BYTES so that its download overlaps the kernel: the one
+ * page-warp driver that ma_warp_pages_host runs, with a single upload piece per page (MICROALIGNER_TRACE_PAGES=1 prints
+ * its timeline).  Synchronous. */
 int ma_warp_affine_flow_pages_host(ma_ctx* ctx, const void* const* pages_host, void* const* out_host, int n_pages,
                                    int dtype, int h, int w, int pad_left, int pad_top, const float* flow, int H, int W,
                                    const double m[6], int interp);

@@ -36,7 +36,8 @@ int ma_warp_tiled_interp(ma_ctx* ctx, const void* img, int dtype, int H, int W, 
                          void* out, int interp);
 
 /* ma_warp_pages_host with the interpolation mode interp: host pages in, host pages out, one device-resident flow,
- * upload, kernel and download overlapped in the bands of ma_warp_pages_plan.  Synchronous. */
+ * upload, kernel and download overlapped in the bands of ma_warp_pages_plan, by the one page-warp driver that
+ * ma_warp_pages_host runs (MICROALIGNER_TRACE_PAGES=1 prints its timeline).  Synchronous. */
 int ma_warp_pages_host_interp(ma_ctx* ctx, const void* const* pages_host, void* const* out_host, int n_pages, int dtype,
                               int H, int W, const float* flow, int tile, int overlap, int interp);
 

@@ -117,6 +117,24 @@ int ma_engine_h2d_pieces(ma_ctx* ctx, int engine, void* dst, const void* src_hos
                          const MaPieceFn& enqueued, bool wait = true);
 int ma_engine_d2h_pieces(ma_ctx* ctx, int engine, void* dst_host, const void* src, size_t bytes, const size_t* cuts, int ncuts,
                          const MaPieceFn& before);
+// The page-warp driver (page_pipeline.hip): host pages in, warped host pages out, through device slots in the context
+// workspace on the three engines.  The three entry points that warp pages check their arguments, fill in a plan and a
+// launch, and run it.
+struct MaPagePlan {
+    size_t in_bytes, out_bytes;      // of one input page, of one output page
+    size_t out_row_bytes;            // of one output row (cuts_out holds whole rows)
+    // ascending end offsets of the pieces a page goes up in: one per band (band b runs once piece b is in), or a single
+    // one (every band waits for the whole page); cuts_src.back() == in_bytes
+    std::vector<size_t> cuts_src;
+    std::vector<size_t> cuts_out;    // ascending end offsets of the output bands; cuts_out.back() == out_bytes
+};
+// enqueues the warp of output rows [y0, y1) of the page at din into dout on the ctx stream; called on the thread that
+// called ma_warp_pages_run, which has the ctx's device set
+typedef std::function<int(const void* din, void* dout, int y0, int y1)> MaBandFn;
+int ma_warp_pages_run(ma_ctx* ctx, const void* const* pages_host, void* const* out_host, int n_pages, const MaPagePlan& plan,
+                      const MaBandFn& launch);
+// the plan of the tiled warps (remap.hip): ma_warp_pages_plan's bands, each uploaded with the `overlap` rows its windows add
+int ma_warp_pages_tiled_plan(int dtype, int H, int W, int tile, int overlap, size_t band_bytes, MaPagePlan* plan);
 // event i of the ctx's pool of timing-free events for ordering its two streams (created on demand; nullptr on failure)
 hipEvent_t ma_ctx_sync_event(ma_ctx* ctx, size_t i);
 // fixed indices beyond the events ma_optflow_register uses (2 per level + 1 <= 65)

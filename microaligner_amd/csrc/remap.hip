@@ -4,81 +4,13 @@
 // Semantics: SURVEY.md Appendix A.2 -- coordinates quantised to 1/32 px with round-half-even,
 // u8 uses the 15-bit fixed-point table, u16/f32 use float weights summed left to right.
 // HBM-bound gathers, rows coalesced along x; the tiled kernels give a thread 8 rows and issue all their loads first.
-#include "ma_internal.h"
+#include "remap_common.h"
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <condition_variable>
-#include <cstring>
-#include <mutex>
-#include <string>
-#include <thread>
 #include <vector>
 
 namespace {
-
-struct Tap {
-    int sx, sy;   // integer source coordinate of the top-left tap
-    int fx, fy;   // 5-bit fractions
-};
-
-__device__ __forceinline__ short d_sat_short(int v) { return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
-
-__device__ __forceinline__ Tap quantise(float mx, float my)
-{
-    int sxq = d_cvround(mx * 32.f), syq = d_cvround(my * 32.f);
-    Tap t;
-    t.fx = sxq & 31; t.fy = syq & 31;
-    t.sx = d_sat_short(sxq >> 5); t.sy = d_sat_short(syq >> 5);
-    return t;
-}
-
-// 15-bit fixed-point bilinear weights of OpenCV's BilinearTab_i (A.2), including the
-// [32767,0,0,1] entry that the table's sum fix-up produces at zero fraction.
-__device__ __forceinline__ void weights_i(int fx, int fy, int w[4])
-{
-    if ((fx | fy) == 0) { w[0] = 32767; w[1] = 0; w[2] = 0; w[3] = 1; return; }
-    w[0] = (32 - fy) * (32 - fx) * 32; w[1] = (32 - fy) * fx * 32;
-    w[2] = fy * (32 - fx) * 32;        w[3] = fy * fx * 32;
-}
-__device__ __forceinline__ void weights_f(int fx, int fy, float w[4])
-{
-    // products of the exact 1-D weights (1 - f/32, f/32): exact in float
-    const float s = 1.f / 32.f;
-    float x1 = fx * s, x0 = 1.f - x1, y1 = fy * s, y0 = 1.f - y1;
-    w[0] = y0 * x0; w[1] = y0 * x1; w[2] = y1 * x0; w[3] = y1 * x1;
-}
-
-template <typename T> struct Interp;
-template <> struct Interp<uint8_t> {
-    __device__ static uint8_t run(uint8_t v0, uint8_t v1, uint8_t v2, uint8_t v3, int fx, int fy)
-    {
-        int w[4];
-        weights_i(fx, fy, w);
-        int acc = v0 * w[0] + v1 * w[1] + v2 * w[2] + v3 * w[3];
-        return (uint8_t)d_clamp((acc + (1 << 14)) >> 15, 0, 255);
-    }
-};
-template <> struct Interp<uint16_t> {
-    __device__ static uint16_t run(uint16_t v0, uint16_t v1, uint16_t v2, uint16_t v3, int fx, int fy)
-    {
-        float w[4];
-        weights_f(fx, fy, w);
-        float acc = (float)v0 * w[0] + (float)v1 * w[1] + (float)v2 * w[2] + (float)v3 * w[3];
-        return (uint16_t)d_clamp(d_cvround(acc), 0, 65535);
-    }
-};
-template <> struct Interp<float> {
-    __device__ static float run(float v0, float v1, float v2, float v3, int fx, int fy)
-    {
-        float w[4];
-        weights_f(fx, fy, w);
-        return v0 * w[0] + v1 * w[1] + v2 * w[2] + v3 * w[3];
-    }
-};
 
 // ---- generic cv2.remap ------------------------------------------------------------------------
 template <typename T, int CN>
@@ -206,34 +138,6 @@ __device__ __forceinline__ void warp_tiled_rows(const T* __restrict__ img, const
         for (int r = 0; r < R; r++) res[r] = warp_tiled_px<T>(img, g, f[r], x, y[r], oy[r], ox);
     }
 }
-
-// Window origin along x of column `x` (ox = (x / T) T - ov) without a division per lane: the 64 columns of a wave lie in at
-// most two windows when T >= 64 -- the wave's first column decides (a scalar division), the columns at or beyond the next
-// window's first take that one.
-__device__ __forceinline__ int warp_window_origin_x(int x, const MaTiling& g)
-{
-    if (g.T <= 0) return 0;
-    if (g.T < 64) return (x / g.T) * g.T - g.ov;
-    const int x_first = __builtin_amdgcn_readfirstlane(x - (int)(threadIdx.x & 63));
-    const int t0 = x_first / g.T, next = (t0 + 1) * g.T;
-    return (x >= next ? next : t0 * g.T) - g.ov;
-}
-// Window origins along y of the rows y0 .. y0 + R of a block: one division, the rows at or beyond the next window's first
-// row take that one (T >= R; smaller tiles divide per row)
-struct WarpRowsY {
-    int t0T, next, T, ov;
-    __device__ __forceinline__ WarpRowsY(int y0, const MaTiling& g) : T(g.T), ov(g.ov)
-    {
-        const int t0 = g.T > 0 ? y0 / g.T : 0;
-        t0T = t0 * g.T; next = t0T + g.T;
-    }
-    __device__ __forceinline__ int origin(int y) const
-    {
-        if (T <= 0) return 0;
-        if (T < 16) return (y / T) * T - ov;
-        return (y >= next ? next : t0T) - ov;
-    }
-};
 
 // floats <-> unsigned keys whose integer order is the float order (so atomicMax works for any sign); every NaN maps
 // to the largest key, so it survives the atomic reduction (numpy's .max() propagates NaN)
@@ -632,15 +536,10 @@ int ma_warp_tiled_flowcells(ma_ctx* ctx, const void* img, int dtype, int H, int 
     return warp_tiled_impl(ctx, img, dtype, H, W, flow, tile, overlap, out, minmax_dev, flow_cellkeys_dev);
 }
 
-// ---- page-warp driver ---------------------------------------------------------------------
-// warp_and_save_pages (microaligner/__main__.py:288-302): every channel / z page of a cycle is warped with the
-// SAME flow.  The flow stays in HBM; pages stream through NS slots (a device buffer pair each) on the three engines
-// of the context, so the upload of one piece, the kernel of the previous one and the download of the one before
-// overlap.  The unit of the pipeline is a BAND of whole tile rows, not a page: an output pixel only reads source
-// pixels of its own window (warper.py:29-76 cuts the windows before cv2.remap sees them), so the rows of tile row
-// ty are complete once source rows < (ty + 1) * tile + overlap have arrived -- a single page (Warper.warp() of a
-// host image, the reference's own per-page loop) overlaps its own upload, kernel and download, and the first and
-// last page of a longer run lose only a band to filling and draining.
+// ---- page-warp driver (the pipeline itself is page_pipeline.hip) ----------------------------------
+// The tiled warps move a page in BANDS of whole tile rows: an output pixel only reads source pixels of its own window
+// (warper.py:29-76 cuts the windows before cv2.remap sees them), so the rows of tile row ty are complete once source
+// rows < (ty + 1) * tile + overlap have arrived, and a page overlaps its own upload, kernel and download.
 int ma_warp_pages_plan(int dtype, int H, int W, int tile, int overlap, size_t band_bytes, int* band_rows, int* n_bands)
 {
     MA_REQUIRE(band_rows && n_bands, "NULL argument");
@@ -670,173 +569,21 @@ int ma_warp_pages_host(ma_ctx* ctx, const void* const* pages_host, void* const* 
     for (int i = 0; i < n_pages; i++) MA_REQUIRE(pages_host[i] && out_host[i], "NULL page pointer");
     if (n_pages == 0) return MA_OK;
     MA_HIP(hipSetDevice(ctx->device));
-    // An upload thread copies band after band into input slot page % NS on the H2D stream, this thread launches the
-    // band's warp on the ctx stream, a download thread copies its rows out on the D2H stream; events order the streams,
-    // counters under one mutex order the threads.  Pageable pages (numpy arrays, rows of a memmapped TIFF) are staged
-    // by the engines through page-locked chunks -- the runtime's own staging of pageable memory reached 14 GB/s per
-    // direction here, the engines 2 - 3 x that (profiles/r04_notes.md).
-    constexpr int NS = 3;
-    const int ns = n_pages < NS ? n_pages : NS;
-    const size_t esz = ma_esize(dtype), rowb = (size_t)W * esz;
-    const size_t nb = (size_t)H * rowb;
-    const size_t bytes = ma_align_up(nb, 256);
-    // bands: whole tile rows, at least MA_OPT_WARP_BAND_BYTES each (32 MiB: a transfer below that no longer runs at the
-    // link rate); an untiled warp (tile == 0: one window) is one band
-    int band_rows = H, nband = 1;
-    MA_TRY(ma_warp_pages_plan(dtype, H, W, tile, overlap, ctx->warp_band_bytes, &band_rows, &nband));
-    const long long n_units = (long long)n_pages * nband;
-    MA_TRY(ma_ws_reserve(ctx, bytes * 2 * ns));  // device buffers come from the context workspace
-    void *din[NS], *dout[NS];
-    std::vector<hipEvent_t> ev_up((size_t)ns * nband, nullptr), ev_k((size_t)ns * nband, nullptr);
-    auto cleanup = [&]() {
-        for (hipEvent_t e : ev_up) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : ev_k) if (e) (void)hipEventDestroy(e);
-    };
-    for (int k = 0; k < ns; k++) {
-        din[k] = (char*)ctx->ws + bytes * (2 * k);
-        dout[k] = (char*)ctx->ws + bytes * (2 * k + 1);
-    }
-    // The slots live in the context workspace, which kernels enqueued earlier on the compute stream (a tiled Farneback,
-    // a dog(), the NMI) may still be using: both transfer engines start behind everything the compute stream holds now
-    // (ma_ws_reserve itself synchronises only when the workspace has to grow).
-    {
-        hipEvent_t ws_idle = ma_ctx_sync_event(ctx, MA_EV_WARP_PAGES);
-        hipStream_t s_up = ma_engine_stream(ctx, MA_ENGINE_H2D), s_down = ma_engine_stream(ctx, MA_ENGINE_D2H);
-        if (!ws_idle || !s_up || !s_down) return MA_EHIP;
-        MA_HIP(hipEventRecord(ws_idle, ctx->stream));
-        MA_HIP(hipStreamWaitEvent(s_up, ws_idle, 0));
-        MA_HIP(hipStreamWaitEvent(s_down, ws_idle, 0));
-    }
-    for (size_t e = 0; e < ev_up.size(); e++)
-        if (hipEventCreateWithFlags(&ev_up[e], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_k[e], hipEventDisableTiming) != hipSuccess) {
-            cleanup();
-            ma_set_error("hipEventCreate failed");
-            return MA_EHIP;
-        }
-    // output rows of band b, and the source rows that must be resident before it runs
-    auto band_begin = [&](int b) { return b * band_rows; };
-    auto band_end = [&](int b) { return std::min(H, (b + 1) * band_rows); };
-    auto src_end = [&](int b) { return b == nband - 1 ? H : std::min(H, (b + 1) * band_rows + g.ov); };
-    // byte offsets at which the bands end: in the source (a band's window reaches `overlap` rows further) and in the result
-    std::vector<size_t> cuts_src(nband), cuts_out(nband);
-    for (int b = 0; b < nband; b++) {
-        cuts_src[b] = (size_t)src_end(b) * rowb;
-        cuts_out[b] = (size_t)band_end(b) * rowb;
-    }
-    const bool TRACE = getenv("MICROALIGNER_TRACE_PAGES") != nullptr;   // timeline of the three threads on stderr
-    const auto T0 = std::chrono::steady_clock::now();
-    auto now_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count(); };
-    if (TRACE) fprintf(stderr, "[pages] %d pages, %d bands of %d rows\n", n_pages, nband, band_rows);
-    std::mutex mu;
-    std::condition_variable cv;
-    long long uploaded = 0, launched = 0;   // in units (page * nband + band)
-    int downloaded = 0;                     // in pages
-    int failed = MA_OK;
-    std::string what;
-    auto fail = [&](int rc) {   // called with mu held
-        if (failed == MA_OK) { failed = rc; what = ma_last_error(); }
-        cv.notify_all();
-    };
-    // A page is ONE copy per direction (ma_engine_*_pieces): the staging of pageable memory keeps its chunks in flight
-    // across the band boundaries, the bands only decide when the events are recorded and waited for.
-    std::thread up([&]() {
-        for (int i = 0; i < n_pages; i++) {
-            const int k = i % ns;
-            {   // slot k is free again once page i - ns has been downloaded
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return failed != MA_OK || downloaded > i - ns; });
-                if (failed != MA_OK) return;
-            }
-            const int rc = ma_engine_h2d_pieces(ctx, MA_ENGINE_H2D, din[k], pages_host[i], nb, cuts_src.data(), nband, [&](int b) {
-                const int r = ma_engine_record(ctx, MA_ENGINE_H2D, ev_up[(size_t)k * nband + b]);
-                if (TRACE) fprintf(stderr, "[pages] %8.2f up   p%d b%d\n", now_ms(), i, b);
-                std::lock_guard<std::mutex> lk(mu);
-                if (r != MA_OK) return r;
-                if (failed != MA_OK) return failed;
-                uploaded = (long long)i * nband + b + 1;
-                cv.notify_all();
-                return (int)MA_OK;
-            }, false);   // no wait at the page boundary: the next page's first chunk is staged under this page's last DMAs
-            if (rc != MA_OK) {
-                std::lock_guard<std::mutex> lk(mu);
-                fail(rc);
-                return;
-            }
-        }
-        const int rc = ma_engine_sync(ctx, MA_ENGINE_H2D);
-        if (rc != MA_OK) {
-            std::lock_guard<std::mutex> lk(mu);
-            fail(rc);
-        }
-    });
-    std::thread down([&]() {
-        for (int i = 0; i < n_pages; i++) {
-            const int k = i % ns;
-            const int rc = ma_engine_d2h_pieces(ctx, MA_ENGINE_D2H, out_host[i], dout[k], nb, cuts_out.data(), nband, [&](int b) {
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return failed != MA_OK || launched > (long long)i * nband + b; });
-                    if (failed != MA_OK) return failed;
-                }
-                if (TRACE) fprintf(stderr, "[pages] %8.2f down p%d b%d (issued)\n", now_ms(), i, b);
-                return ma_engine_wait(ctx, MA_ENGINE_D2H, ev_k[(size_t)k * nband + b]);
-            });
-            std::lock_guard<std::mutex> lk(mu);
-            if (rc != MA_OK) { fail(rc); return; }
-            if (TRACE) fprintf(stderr, "[pages] %8.2f down p%d complete\n", now_ms(), i);
-            downloaded = i + 1;
-            cv.notify_all();
-        }
-    });
+    MaPagePlan plan;
+    MA_TRY(ma_warp_pages_tiled_plan(dtype, H, W, tile, overlap, ctx->warp_band_bytes, &plan));
     const float2* f = (const float2*)flow;
-    const dim3 block(256);
-    for (long long u = 0; u < n_units; u++) {
-        const int i = (int)(u / nband), b = (int)(u % nband), k = i % ns;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return failed != MA_OK || uploaded > u; });
-            if (failed != MA_OK) break;
-        }
-        const int y0 = band_begin(b), y1 = band_end(b);
-        const dim3 grid((W + 255) / 256, (y1 - y0 + WARP_ROWS - 1) / WARP_ROWS);
-        hipError_t e = hipStreamWaitEvent(ctx->stream, ev_up[(size_t)k * nband + b], 0);
-        if (e == hipSuccess) {
-#define MA_BAND(T) do { if (idx32) hipLaunchKernelGGL((warp_band_kernel<T, true>), grid, block, 0, ctx->stream, (const T*)din[k], g, f, (T*)dout[k], y0, y1); \
-                        else hipLaunchKernelGGL((warp_band_kernel<T, false>), grid, block, 0, ctx->stream, (const T*)din[k], g, f, (T*)dout[k], y0, y1); } while (0)
-            const bool idx32 = (unsigned long long)H * (unsigned long long)W < (1ull << 31);
-            if (dtype == MA_U8) MA_BAND(uint8_t);
-            else if (dtype == MA_U16) MA_BAND(uint16_t);
-            else MA_BAND(float);
+    const bool idx32 = (unsigned long long)H * (unsigned long long)W < (1ull << 31);
+    return ma_warp_pages_run(ctx, pages_host, out_host, n_pages, plan, [&](const void* din, void* dout, int y0, int y1) -> int {
+        const dim3 grid((W + 255) / 256, (y1 - y0 + WARP_ROWS - 1) / WARP_ROWS), block(256);
+#define MA_BAND(T) do { if (idx32) hipLaunchKernelGGL((warp_band_kernel<T, true>), grid, block, 0, ctx->stream, (const T*)din, g, f, (T*)dout, y0, y1); \
+                        else hipLaunchKernelGGL((warp_band_kernel<T, false>), grid, block, 0, ctx->stream, (const T*)din, g, f, (T*)dout, y0, y1); } while (0)
+        if (dtype == MA_U8) MA_BAND(uint8_t);
+        else if (dtype == MA_U16) MA_BAND(uint16_t);
+        else MA_BAND(float);
 #undef MA_BAND
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(ev_k[(size_t)k * nband + b], ctx->stream);
-        if (TRACE) fprintf(stderr, "[pages] %8.2f kern p%d b%d\n", now_ms(), i, b);
-        std::lock_guard<std::mutex> lk(mu);
-        if (e != hipSuccess) {
-            ma_set_error("warp of page %d (rows %d..%d) failed: %s", i, y0, y1, hipGetErrorString(e));
-            fail(MA_EHIP);
-            break;
-        }
-        launched = u + 1;
-        cv.notify_all();
-    }
-    up.join();
-    down.join();
-    if (TRACE) fprintf(stderr, "[pages] %8.2f joined\n", now_ms());
-    // also when a thread gave up early: nothing of this call may still be reading the caller's pages or writing its
-    // results once it has returned
-    (void)ma_engine_sync(ctx, MA_ENGINE_H2D);
-    (void)ma_engine_sync(ctx, MA_ENGINE_D2H);
-    (void)hipStreamSynchronize(ctx->stream);
-    cleanup();
-    if (TRACE) fprintf(stderr, "[pages] %8.2f cleaned\n", now_ms());
-    if (failed != MA_OK) {
-        ma_set_error("%s", what.c_str());
-        return failed;
-    }
-    return MA_OK;
+        MA_HIP(hipGetLastError());
+        return MA_OK;
+    });
 }
 
 int ma_merge_flows_tiled(ma_ctx* ctx, const float* flow1, const float* flow2, int H, int W, int tile, int overlap,
@@ -895,3 +642,22 @@ int ma_merge_flows_tiled_cells(ma_ctx* ctx, const float* flow1, const float* flo
 }
 
 } // extern "C"
+
+// The plan of a tiled page warp: bands of whole tile rows, at least band_bytes each (MA_OPT_WARP_BAND_BYTES, 32 MiB: a
+// transfer below that no longer runs at the link rate); an untiled warp (tile == 0: one window) is one band.  A page goes
+// up in one piece per band, which ends `overlap` rows beyond the band (its windows reach that far).
+int ma_warp_pages_tiled_plan(int dtype, int H, int W, int tile, int overlap, size_t band_bytes, MaPagePlan* plan)
+{
+    int band_rows = H, nband = 1;
+    MA_TRY(ma_warp_pages_plan(dtype, H, W, tile, overlap, band_bytes, &band_rows, &nband));
+    const size_t rowb = (size_t)W * ma_esize(dtype);
+    plan->in_bytes = plan->out_bytes = (size_t)H * rowb;
+    plan->out_row_bytes = rowb;
+    plan->cuts_src.resize(nband);
+    plan->cuts_out.resize(nband);
+    for (int b = 0; b < nband; b++) {
+        plan->cuts_src[b] = (size_t)(b == nband - 1 ? H : std::min(H, (b + 1) * band_rows + overlap)) * rowb;
+        plan->cuts_out[b] = (size_t)std::min(H, (b + 1) * band_rows) * rowb;
+    }
+    return MA_OK;
+}

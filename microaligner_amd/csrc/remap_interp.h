@@ -1,11 +1,11 @@
 // Tap and weight code of cv2.remap's INTER_NEAREST / INTER_CUBIC / INTER_LANCZOS4 shared by the kernels of
-// remap_interp.hip and warp_compose.hip: the 5-bit quantisation, the 1-D weight tables in constant memory (one copy per
-// source file that includes this header, filled by its own ensure_tables()), their LDS staging, and the sample of N x N taps
-// in OpenCV's summation order.  The semantics are those of include/microaligner_interp.h.
+// remap_interp.hip and warp_compose.hip: the 1-D weight tables in constant memory (one copy per source file that includes
+// this header, filled by its own ensure_tables()), their LDS staging, and the sample of N x N taps in OpenCV's summation
+// order; the 5-bit quantisation is remap_common.h's.  The semantics are those of include/microaligner_interp.h.
 #ifndef MA_REMAP_INTERP_H
 #define MA_REMAP_INTERP_H
 
-#include "ma_internal.h"
+#include "remap_common.h"
 #include "../../include/microaligner_interp.h"
 
 #include <climits>
@@ -31,22 +31,8 @@ template <> struct Mode<MA_INTER_LANCZOS4> { static constexpr int N = 8, OFF = 3
 template <int N> __device__ __forceinline__ const float* d_tab1() { return N == 4 ? c_tab_cubic : c_tab_lanczos; }
 template <int N> __device__ __forceinline__ const int* d_fix() { return N == 4 ? c_fix_cubic : c_fix_lanczos; }
 
-__device__ __forceinline__ short d_sat_short(int v) { return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
 // (unsigned)v < max(n, 0): OpenCV's width1 tests
 __device__ __forceinline__ bool d_below(int v, int n) { return n > 0 && (unsigned)v < (unsigned)n; }
-
-struct Tap {
-    int sx, sy;   // integer source coordinate (before the tap offset)
-    int fx, fy;   // 5-bit fractions
-};
-__device__ __forceinline__ Tap quantise(float mx, float my)
-{
-    int sxq = d_cvround(mx * 32.f), syq = d_cvround(my * 32.f);
-    Tap t;
-    t.fx = sxq & 31; t.fy = syq & 31;
-    t.sx = d_sat_short(sxq >> 5); t.sy = d_sat_short(syq >> 5);
-    return t;
-}
 
 // stage the 1-D table of the mode in LDS (every thread of the block takes part: before any early return)
 template <int N>

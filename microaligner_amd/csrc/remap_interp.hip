@@ -2,7 +2,7 @@
 // tiled warp of Warper.warp() and the page-warp driver.  Off the measured path: remap.hip keeps the linear kernels, and
 // MA_INTER_LINEAR forwards to them.
 //
-// Coordinates are quantised as remap.hip's quantise() does (1/32 px, cvRound); nearest rounds each coordinate on its own.
+// Coordinates are quantised by remap_common.h's quantise() (1/32 px, cvRound); nearest rounds each coordinate on its own.
 // The 1-D weight tables are built once per device on the host (interpolateCubic in float, interpolateLanczos4 with sin /
 // cos in double) and staged in LDS by every block; u8 forms its 15-bit 2-D weights from them plus the one correction of
 // initInterTab2D's sum fix-up, a (tap, delta) pair per fraction pair.  Every sample picks OpenCV's summation order: all
@@ -14,12 +14,6 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <condition_variable>
-#include <cstring>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
 
 namespace {
 
@@ -73,30 +67,7 @@ __global__ __launch_bounds__(256) void remap_interp_kernel(const T* __restrict__
 }
 
 // ---- Warper.warp(): window-local map = float(x_local) - flow, the zero-padded window is the source ------------------
-// Window origins, as remap.hip states them for the linear kernels (restated here, not shared, so that remap.hip stays
-// as the measured path has it).
-__device__ __forceinline__ int warp_window_origin_x(int x, const MaTiling& g)
-{
-    if (g.T <= 0) return 0;
-    if (g.T < 64) return (x / g.T) * g.T - g.ov;
-    const int x_first = __builtin_amdgcn_readfirstlane(x - (int)(threadIdx.x & 63));
-    const int t0 = x_first / g.T, next = (t0 + 1) * g.T;
-    return (x >= next ? next : t0 * g.T) - g.ov;
-}
-struct WarpRowsY {
-    int t0T, next, T, ov;
-    __device__ __forceinline__ WarpRowsY(int y0, const MaTiling& g) : T(g.T), ov(g.ov)
-    {
-        const int t0 = g.T > 0 ? y0 / g.T : 0;
-        t0T = t0 * g.T; next = t0T + g.T;
-    }
-    __device__ __forceinline__ int origin(int y) const
-    {
-        if (T <= 0) return 0;
-        if (T < 16) return (y / T) * T - ov;
-        return (y >= next ? next : t0T) - ov;
-    }
-};
+// (the window origins are remap_common.h's, shared with the linear kernels)
 
 // one sample of the window at (ox, oy), tap origin (sx, sy) window-local: taps beyond the window are not read (skipped
 // by the sum unless every tap is inside it), taps in the window's zero padding read 0
@@ -280,10 +251,8 @@ int ma_warp_tiled_interp(ma_ctx* ctx, const void* img, int dtype, int H, int W, 
     return launch_warp(ctx, img, dtype, g, (const float2*)flow, out, 0, H, interp);
 }
 
-// Page-warp driver with the interpolation modes: ma_warp_pages_host's pipeline, built from ma_warp_pages_plan, the engine
-// and event calls.  An upload thread copies band after band of page i into input slot i % NS on the H2D engine, this
-// thread launches each band's warp on the compute engine once its source rows are in, a download thread copies the band's
-// output rows out on the D2H engine; events order the engines, counters under one mutex order the threads.
+// Page-warp driver with the interpolation modes: the bands and upload pieces of ma_warp_pages_host on the one pipeline
+// (page_pipeline.hip), with this file's kernel on each band.
 int ma_warp_pages_host_interp(ma_ctx* ctx, const void* const* pages_host, void* const* out_host, int n_pages, int dtype,
                               int H, int W, const float* flow, int tile, int overlap, int interp)
 {
@@ -294,143 +263,17 @@ int ma_warp_pages_host_interp(ma_ctx* ctx, const void* const* pages_host, void* 
     MA_REQUIRE(n_pages >= 0, "bad page count");
     long long band_bytes = 0;
     MA_TRY(ma_ctx_get_option(ctx, MA_OPT_WARP_BAND_BYTES, &band_bytes));
-    int band_rows = H, nband = 1;
-    MA_TRY(ma_warp_pages_plan(dtype, H, W, tile, overlap, (size_t)band_bytes, &band_rows, &nband));
+    MaPagePlan plan;
+    MA_TRY(ma_warp_pages_tiled_plan(dtype, H, W, tile, overlap, (size_t)band_bytes, &plan));
     const MaTiling g = ma_make_tiling(H, W, tile, overlap);
     MA_REQUIRE(g.Ph < 32767 && g.Pw < 32767, "cv2.remap requires window dimensions < 32767");
     for (int i = 0; i < n_pages; i++) MA_REQUIRE(pages_host[i] && out_host[i], "NULL page pointer");
     if (n_pages == 0) return MA_OK;
     MA_HIP(hipSetDevice(ctx->device));
     MA_TRY(ensure_tables(ctx));
-
-    constexpr int NS = 3;
-    const int ns = n_pages < NS ? n_pages : NS;
-    const size_t rowb = (size_t)W * ma_esize(dtype), nb = (size_t)H * rowb, bytes = ma_align_up(nb, 256);
-    MA_TRY(ma_ws_reserve(ctx, bytes * 2 * ns));   // device slots in the context workspace
-    char *din[NS], *dout[NS];
-    for (int k = 0; k < ns; k++) {
-        din[k] = (char*)ctx->ws + bytes * (2 * k);
-        dout[k] = (char*)ctx->ws + bytes * (2 * k + 1);
-    }
-    std::vector<void*> ev_up((size_t)ns * nband, nullptr), ev_k((size_t)ns * nband, nullptr);
-    void* ws_idle = nullptr;
-    auto cleanup = [&]() {
-        for (void* e : ev_up) if (e) (void)ma_event_destroy(ctx, e);
-        for (void* e : ev_k) if (e) (void)ma_event_destroy(ctx, e);
-        if (ws_idle) (void)ma_event_destroy(ctx, ws_idle);
-    };
-    int rc = ma_event_create(ctx, &ws_idle);
-    for (size_t e = 0; rc == MA_OK && e < ev_up.size(); e++) {
-        rc = ma_event_create(ctx, &ev_up[e]);
-        if (rc == MA_OK) rc = ma_event_create(ctx, &ev_k[e]);
-    }
-    // the slots may still be in use by kernels enqueued earlier on the compute stream: both transfer engines start behind
-    // everything it holds now
-    if (rc == MA_OK) rc = ma_engine_record(ctx, MA_ENGINE_COMPUTE, ws_idle);
-    if (rc == MA_OK) rc = ma_engine_wait(ctx, MA_ENGINE_H2D, ws_idle);
-    if (rc == MA_OK) rc = ma_engine_wait(ctx, MA_ENGINE_D2H, ws_idle);
-    if (rc != MA_OK) {
-        cleanup();
-        return rc;
-    }
-    // output rows of band b, and the source rows that must be resident before it runs
-    auto band_begin = [&](int b) { return b * band_rows; };
-    auto band_end = [&](int b) { return std::min(H, (b + 1) * band_rows); };
-    auto src_end = [&](int b) { return b == nband - 1 ? H : std::min(H, (b + 1) * band_rows + g.ov); };
-
-    std::mutex mu;
-    std::condition_variable cv;
-    long long uploaded = 0, launched = 0;   // in units (page * nband + band)
-    int downloaded = 0;                     // in pages
-    int failed = MA_OK;
-    std::string what;
-    auto fail = [&](int r) {   // called with mu held
-        if (failed == MA_OK) { failed = r; what = ma_last_error(); }
-        cv.notify_all();
-    };
-    // byte offsets at which the bands end: in the source (a band's window reaches `overlap` rows further) and in the result.
-    // A page is ONE copy per direction in pieces (ma_engine_*_pieces): the staging of pageable memory keeps its chunks in
-    // flight across the band boundaries, the bands only decide where the events are recorded and waited for.
-    std::vector<size_t> cuts_src(nband), cuts_out(nband);
-    for (int b = 0; b < nband; b++) {
-        cuts_src[b] = (size_t)src_end(b) * rowb;
-        cuts_out[b] = (size_t)band_end(b) * rowb;
-    }
-    std::thread up([&]() {
-        for (int i = 0; i < n_pages; i++) {
-            const int k = i % ns;
-            {   // slot k is free again once page i - ns has been downloaded
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return failed != MA_OK || downloaded > i - ns; });
-                if (failed != MA_OK) return;
-            }
-            const int r = ma_engine_h2d_pieces(ctx, MA_ENGINE_H2D, din[k], pages_host[i], nb, cuts_src.data(), nband, [&](int b) {
-                const int rr = ma_engine_record(ctx, MA_ENGINE_H2D, ev_up[(size_t)k * nband + b]);
-                std::lock_guard<std::mutex> lk(mu);
-                if (rr != MA_OK) return rr;
-                if (failed != MA_OK) return failed;
-                uploaded = (long long)i * nband + b + 1;
-                cv.notify_all();
-                return (int)MA_OK;
-            }, false);   // no wait at the page boundary: the next page's first chunk is staged under this page's last DMAs
-            if (r != MA_OK) {
-                std::lock_guard<std::mutex> lk(mu);
-                fail(r);
-                return;
-            }
-        }
-        const int r = ma_engine_sync(ctx, MA_ENGINE_H2D);
-        if (r != MA_OK) {
-            std::lock_guard<std::mutex> lk(mu);
-            fail(r);
-        }
+    return ma_warp_pages_run(ctx, pages_host, out_host, n_pages, plan, [&](const void* din, void* dout, int y0, int y1) {
+        return launch_warp(ctx, din, dtype, g, (const float2*)flow, dout, y0, y1, interp);
     });
-    std::thread down([&]() {
-        for (int i = 0; i < n_pages; i++) {
-            const int k = i % ns;
-            const int r = ma_engine_d2h_pieces(ctx, MA_ENGINE_D2H, out_host[i], dout[k], nb, cuts_out.data(), nband, [&](int b) {
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return failed != MA_OK || launched > (long long)i * nband + b; });
-                    if (failed != MA_OK) return failed;
-                }
-                return ma_engine_wait(ctx, MA_ENGINE_D2H, ev_k[(size_t)k * nband + b]);
-            });
-            std::lock_guard<std::mutex> lk(mu);
-            if (r != MA_OK) { fail(r); return; }
-            downloaded = i + 1;
-            cv.notify_all();
-        }
-    });
-    const long long n_units = (long long)n_pages * nband;
-    for (long long u = 0; u < n_units; u++) {
-        const int i = (int)(u / nband), b = (int)(u % nband), k = i % ns;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return failed != MA_OK || uploaded > u; });
-            if (failed != MA_OK) break;
-        }
-        int r = ma_engine_wait(ctx, MA_ENGINE_COMPUTE, ev_up[(size_t)k * nband + b]);
-        if (r == MA_OK) r = launch_warp(ctx, din[k], dtype, g, (const float2*)flow, dout[k], band_begin(b), band_end(b), interp);
-        if (r == MA_OK) r = ma_engine_record(ctx, MA_ENGINE_COMPUTE, ev_k[(size_t)k * nband + b]);
-        std::lock_guard<std::mutex> lk(mu);
-        if (r != MA_OK) { fail(r); break; }
-        launched = u + 1;
-        cv.notify_all();
-    }
-    up.join();
-    down.join();
-    // also when a thread gave up early: nothing of this call may still be reading the caller's pages or writing its
-    // results once it has returned
-    (void)ma_engine_sync(ctx, MA_ENGINE_H2D);
-    (void)ma_engine_sync(ctx, MA_ENGINE_D2H);
-    (void)hipStreamSynchronize(ctx->stream);
-    cleanup();
-    if (failed != MA_OK) {
-        ma_set_error("%s", what.c_str());
-        return failed;
-    }
-    return MA_OK;
 }
 
 } // extern "C"

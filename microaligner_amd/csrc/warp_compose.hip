@@ -5,7 +5,7 @@
 // The map is evaluated in float64 with every multiply and add rounded on its own (__dmul_rn / __dadd_rn), so that a plain
 // numpy float64 statement reproduces it bit for bit.  The sample is cv2.remap's on the zero-padded (H, W) source, which is
 // never built: a tap reads the (h, w) image at (sx - left, sy - top) and 0 outside it.  Nearest, cubic and Lanczos-4 take
-// their taps and weights from remap_interp.h (shared with remap_interp.hip); the linear sample restates remap.hip's.
+// their taps and weights from remap_interp.h (shared with remap_interp.hip), linear takes remap_common.h's bilinear sample.
 //
 // A block covers a 2-D tile of the output, 64 columns by 4 waves x R rows, so that the source footprint stays compact when
 // the matrix rotates; a thread takes R rows of one column and, when every tap of its wave lies inside the image, issues all
@@ -14,50 +14,8 @@
 #include "../../include/microaligner_compose.h"
 
 #include <algorithm>
-#include <condition_variable>
-#include <cstring>
-#include <string>
-#include <thread>
 
 namespace {
-
-// ---- the linear sample ----------------------------------------------------------------------------------------------
-// remap.hip's weights_i / weights_f / Interp<T> (cv2.remap INTER_LINEAR), restated here rather
-// than shared: remap.hip is on the measured path and under build.source_hash(), and stays as the measured path has it
-// (remap_interp.hip restates its window origins for the same reason).
-
-// 15-bit fixed-point bilinear weights of OpenCV's BilinearTab_i, including the [32767,0,0,1] entry that the table's sum
-// fix-up produces at zero fraction
-__device__ __forceinline__ void lin_weights_i(int fx, int fy, int w[4])
-{
-    if ((fx | fy) == 0) { w[0] = 32767; w[1] = 0; w[2] = 0; w[3] = 1; return; }
-    w[0] = (32 - fy) * (32 - fx) * 32; w[1] = (32 - fy) * fx * 32;
-    w[2] = fy * (32 - fx) * 32;        w[3] = fy * fx * 32;
-}
-__device__ __forceinline__ void lin_weights_f(int fx, int fy, float w[4])
-{
-    // products of the exact 1-D weights (1 - f/32, f/32): exact in float
-    const float s = 1.f / 32.f;
-    float x1 = fx * s, x0 = 1.f - x1, y1 = fy * s, y0 = 1.f - y1;
-    w[0] = y0 * x0; w[1] = y0 * x1; w[2] = y1 * x0; w[3] = y1 * x1;
-}
-// the four taps (top left, top right, bottom left, bottom right) summed in that order; taps outside the source hold 0
-template <typename T>
-__device__ __forceinline__ T lin_sample(const T (&v)[2][2], int fx, int fy)
-{
-    if constexpr (sizeof(T) == 1) {
-        int w[4];
-        lin_weights_i(fx, fy, w);
-        const int acc = v[0][0] * w[0] + v[0][1] * w[1] + v[1][0] * w[2] + v[1][1] * w[3];
-        return (T)d_clamp((acc + (1 << 14)) >> 15, 0, 255);
-    } else {
-        float w[4];
-        lin_weights_f(fx, fy, w);
-        const float acc = (float)v[0][0] * w[0] + (float)v[0][1] * w[1] + (float)v[1][0] * w[2] + (float)v[1][1] * w[3];
-        if constexpr (sizeof(T) == 2) return (T)d_clamp(d_cvround(acc), 0, 65535);
-        else return acc;
-    }
-}
 
 // ---- the map --------------------------------------------------------------------------------------------------------
 struct ComposeArgs {
@@ -75,7 +33,7 @@ __device__ __forceinline__ float2 compose_map(const ComposeArgs& a, int x, int y
                        (float)__dadd_rn(__dadd_rn(__dmul_rn(a.m[3], qx), __dmul_rn(a.m[4], qy)), a.m[5]));
 }
 
-// remap_interp.h's quantise() without the saturation of the integer part to 16 bits: sides of 32767 px and more work.
+// remap_common.h's quantise() without the saturation of the integer part to 16 bits: sides of 32767 px and more work.
 // A coordinate that cvRound sends to INT_MIN lands at -2^26, far outside any source.
 __device__ __forceinline__ Tap quantise_wide(float2 m)
 {
@@ -118,7 +76,7 @@ __device__ __forceinline__ T compose_px(const T* __restrict__ img, const Compose
         for (int k2 = 0; k2 < N; k2++)
             v[k1][k2] = ((rimg >> k1) & (cimg >> k2) & 1u) ? img[(size_t)(sy + k1 - a.top) * a.w + (sx + k2 - a.left)] : (T)0;
     if constexpr (MODE == MA_INTER_LINEAR) {
-        return lin_sample<T>(v, t.fx, t.fy);
+        return Interp<T>::run(v[0][0], v[0][1], v[1][0], v[1][1], t.fx, t.fy);
     } else {
         const bool fast = d_below(sx, a.W - N + 1) && d_below(sy, a.H - N + 1);
         return combine<T, N>(v, s_tab, t.fx, t.fy, fast, rmask, cmask);
@@ -188,7 +146,8 @@ __global__ __launch_bounds__(256) void warp_compose_kernel(const T* __restrict__
                 }
 #pragma unroll
                 for (int r = 0; r < R; r++) {
-                    if constexpr (MODE == MA_INTER_LINEAR) res[r] = lin_sample<T>(v[r], t[r].fx, t[r].fy);
+                    if constexpr (MODE == MA_INTER_LINEAR)
+                        res[r] = Interp<T>::run(v[r][0][0], v[r][0][1], v[r][1][0], v[r][1][1], t[r].fx, t[r].fy);
                     else res[r] = combine<T, N>(v[r], s_tab, t[r].fx, t[r].fy, true, ~0u, ~0u);
                 }
             } else {
@@ -272,11 +231,10 @@ int ma_warp_affine_flow(ma_ctx* ctx, const void* img, int dtype, int h, int w, i
                           interp);
 }
 
-// Page driver: ma_warp_pages_host_interp's pipeline on the three engines with NS slots, except that a page goes up whole
-// (without a pass over the flow the source rows an output band reads are not bounded) and only the output is cut into
-// bands.  An upload thread copies page i into input slot i % NS on the H2D engine while this thread launches the bands of
-// page i - 1 on the compute engine, and a download thread copies each band's output rows out on the D2H engine as soon as
-// its kernel has run; events order the engines, counters under one mutex order the threads.
+// Page driver: the one pipeline (page_pipeline.hip), except that a page goes up whole (without a pass over the flow the
+// source rows an output band reads are not bounded) and only the output is cut into bands, of MA_OPT_WARP_BAND_BYTES and
+// no tile alignment: page i goes up while the bands of page i - 1 are launched, and each band's rows come down as soon as
+// its kernel has run.
 int ma_warp_affine_flow_pages_host(ma_ctx* ctx, const void* const* pages_host, void* const* out_host, int n_pages,
                                    int dtype, int h, int w, int pad_left, int pad_top, const float* flow, int H, int W,
                                    const double m[6], int interp)
@@ -291,135 +249,17 @@ int ma_warp_affine_flow_pages_host(ma_ctx* ctx, const void* const* pages_host, v
     MA_HIP(hipSetDevice(ctx->device));
     MA_TRY(ensure_tables(ctx));
     const ComposeArgs args = make_args(h, w, pad_left, pad_top, H, W, m);
-
-    constexpr int NS = 3;
-    const int ns = n_pages < NS ? n_pages : NS;
-    const size_t es = ma_esize(dtype), rowb = (size_t)W * es, nb_in = (size_t)h * w * es, nb_out = (size_t)H * rowb;
+    const size_t rowb = (size_t)W * ma_esize(dtype);
     const int band_rows = (int)std::min<size_t>((size_t)H, std::max<size_t>(1, ((size_t)band_bytes + rowb - 1) / rowb));
-    const int nband = (H + band_rows - 1) / band_rows;
-    const size_t in_bytes = ma_align_up(nb_in, 256), out_bytes = ma_align_up(nb_out, 256);
-    MA_TRY(ma_ws_reserve(ctx, (in_bytes + out_bytes) * ns));   // device slots in the context workspace
-    char *din[NS], *dout[NS];
-    for (int k = 0; k < ns; k++) {
-        din[k] = (char*)ctx->ws + (in_bytes + out_bytes) * k;
-        dout[k] = din[k] + in_bytes;
-    }
-    std::vector<void*> ev_up((size_t)ns, nullptr), ev_k((size_t)ns * nband, nullptr);
-    void* ws_idle = nullptr;
-    auto cleanup = [&]() {
-        for (void* e : ev_up) if (e) (void)ma_event_destroy(ctx, e);
-        for (void* e : ev_k) if (e) (void)ma_event_destroy(ctx, e);
-        if (ws_idle) (void)ma_event_destroy(ctx, ws_idle);
-    };
-    int rc = ma_event_create(ctx, &ws_idle);
-    for (size_t e = 0; rc == MA_OK && e < ev_up.size(); e++) rc = ma_event_create(ctx, &ev_up[e]);
-    for (size_t e = 0; rc == MA_OK && e < ev_k.size(); e++) rc = ma_event_create(ctx, &ev_k[e]);
-    // the slots may still be in use by kernels enqueued earlier on the compute stream: both transfer engines start behind
-    // everything it holds now
-    if (rc == MA_OK) rc = ma_engine_record(ctx, MA_ENGINE_COMPUTE, ws_idle);
-    if (rc == MA_OK) rc = ma_engine_wait(ctx, MA_ENGINE_H2D, ws_idle);
-    if (rc == MA_OK) rc = ma_engine_wait(ctx, MA_ENGINE_D2H, ws_idle);
-    if (rc != MA_OK) {
-        cleanup();
-        return rc;
-    }
-    auto band_begin = [&](int b) { return b * band_rows; };
-    auto band_end = [&](int b) { return std::min(H, (b + 1) * band_rows); };
-    std::vector<size_t> cuts_out(nband);
-    for (int b = 0; b < nband; b++) cuts_out[b] = (size_t)band_end(b) * rowb;
-
-    std::mutex mu;
-    std::condition_variable cv;
-    int uploaded = 0, downloaded = 0;   // in pages
-    long long launched = 0;             // in units (page * nband + band)
-    int failed = MA_OK;
-    std::string what;
-    auto fail = [&](int r) {   // called with mu held
-        if (failed == MA_OK) { failed = r; what = ma_last_error(); }
-        cv.notify_all();
-    };
-    std::thread up([&]() {
-        for (int i = 0; i < n_pages; i++) {
-            const int k = i % ns;
-            {   // slot k is free again once page i - ns has been downloaded
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return failed != MA_OK || downloaded > i - ns; });
-                if (failed != MA_OK) return;
-            }
-            const int r = ma_engine_h2d_pieces(ctx, MA_ENGINE_H2D, din[k], pages_host[i], nb_in, &nb_in, 1, [&](int) {
-                const int rr = ma_engine_record(ctx, MA_ENGINE_H2D, ev_up[k]);
-                std::lock_guard<std::mutex> lk(mu);
-                if (rr != MA_OK) return rr;
-                if (failed != MA_OK) return failed;
-                uploaded = i + 1;
-                cv.notify_all();
-                return (int)MA_OK;
-            }, false);   // no wait at the page boundary: the next page's first chunk is staged under this page's last DMAs
-            if (r != MA_OK) {
-                std::lock_guard<std::mutex> lk(mu);
-                fail(r);
-                return;
-            }
-        }
-        const int r = ma_engine_sync(ctx, MA_ENGINE_H2D);
-        if (r != MA_OK) {
-            std::lock_guard<std::mutex> lk(mu);
-            fail(r);
-        }
+    MaPagePlan plan;
+    plan.in_bytes = (size_t)h * w * ma_esize(dtype);
+    plan.out_bytes = (size_t)H * rowb;
+    plan.out_row_bytes = rowb;
+    plan.cuts_src.assign(1, plan.in_bytes);
+    for (int y = 0; y < H; y += band_rows) plan.cuts_out.push_back((size_t)std::min(H, y + band_rows) * rowb);
+    return ma_warp_pages_run(ctx, pages_host, out_host, n_pages, plan, [&](const void* din, void* dout, int y0, int y1) {
+        return launch_compose(ctx, din, dtype, args, (const float2*)flow, dout, y0, y1, interp);
     });
-    std::thread down([&]() {
-        for (int i = 0; i < n_pages; i++) {
-            const int k = i % ns;
-            const int r = ma_engine_d2h_pieces(ctx, MA_ENGINE_D2H, out_host[i], dout[k], nb_out, cuts_out.data(), nband, [&](int b) {
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return failed != MA_OK || launched > (long long)i * nband + b; });
-                    if (failed != MA_OK) return failed;
-                }
-                return ma_engine_wait(ctx, MA_ENGINE_D2H, ev_k[(size_t)k * nband + b]);
-            });
-            std::lock_guard<std::mutex> lk(mu);
-            if (r != MA_OK) { fail(r); return; }
-            downloaded = i + 1;
-            cv.notify_all();
-        }
-    });
-    for (int i = 0; i < n_pages; i++) {
-        const int k = i % ns;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return failed != MA_OK || uploaded > i; });
-            if (failed != MA_OK) break;
-        }
-        int r = ma_engine_wait(ctx, MA_ENGINE_COMPUTE, ev_up[k]);
-        for (int b = 0; r == MA_OK && b < nband; b++) {
-            r = launch_compose(ctx, din[k], dtype, args, (const float2*)flow, dout[k], band_begin(b), band_end(b), interp);
-            if (r == MA_OK) r = ma_engine_record(ctx, MA_ENGINE_COMPUTE, ev_k[(size_t)k * nband + b]);
-            if (r == MA_OK) {
-                std::lock_guard<std::mutex> lk(mu);
-                launched = (long long)i * nband + b + 1;
-                cv.notify_all();
-            }
-        }
-        if (r != MA_OK) {
-            std::lock_guard<std::mutex> lk(mu);
-            fail(r);
-            break;
-        }
-    }
-    up.join();
-    down.join();
-    // also when a thread gave up early: nothing of this call may still be reading the caller's pages or writing its
-    // results once it has returned
-    (void)ma_engine_sync(ctx, MA_ENGINE_H2D);
-    (void)ma_engine_sync(ctx, MA_ENGINE_D2H);
-    (void)hipStreamSynchronize(ctx->stream);
-    cleanup();
-    if (failed != MA_OK) {
-        ma_set_error("%s", what.c_str());
-        return failed;
-    }
-    return MA_OK;
 }
 
 } // extern "C"

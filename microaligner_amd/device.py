@@ -679,6 +679,18 @@ class Context:
                                            int(overlap), out.ptr)
         return out
 
+    @staticmethod
+    def _page_pointers(pages, out, out_shape, out_what):
+        """The results of a page warp (allocated if `out` is None, checked otherwise) and the two pointer arrays the
+        page-warp entry points take: (out, n, src, dst)."""
+        if out is None:
+            out = [np.empty(out_shape, pages[0].dtype) for _ in pages]
+        if len(out) != len(pages) or any(o.shape != out_shape or o.dtype != pages[0].dtype or not o.flags.c_contiguous
+                                         or not o.flags.writeable for o in out):
+            raise ValueError(f"out must hold one writable C-contiguous array of {out_what} per page")
+        n = len(pages)
+        return out, n, (C.c_void_p * n)(*[p.ctypes.data for p in pages]), (C.c_void_p * n)(*[o.ctypes.data for o in out])
+
     def warp_pages(self, pages, flow, tile, overlap, out=None, interpolation="linear"):
         """warp_and_save_pages (__main__.py:288-302): warp every HOST page with one device-resident flow.
         pages: sequence of equal-shape C-contiguous numpy arrays; out: optional sequence of writable arrays of the
@@ -695,14 +707,7 @@ class Context:
             raise ValueError(f"flow must be float32 of shape {(H, W, 2)}, got {flow.dtype} {flow.shape}")
         if getattr(flow, "ctx", self) is not self:
             raise ValueError("flow belongs to another context")
-        if out is None:
-            out = [np.empty((H, W), pages[0].dtype) for _ in pages]
-        if len(out) != len(pages) or any(o.shape != (H, W) or o.dtype != pages[0].dtype or not o.flags.c_contiguous
-                                         or not o.flags.writeable for o in out):
-            raise ValueError("out must hold one writable C-contiguous array of the page shape/dtype per page")
-        n = len(pages)
-        src = (C.c_void_p * n)(*[p.ctypes.data for p in pages])
-        dst = (C.c_void_p * n)(*[o.ctypes.data for o in out])
+        out, n, src, dst = self._page_pointers(pages, out, (H, W), "the page shape/dtype")
         if interp == L.MA_INTER_LINEAR:
             self._run(self.lib.ma_warp_pages_host, src, dst, n, dt, H, W, flow.ptr, int(tile), int(overlap))
         else:
@@ -738,14 +743,7 @@ class Context:
         if getattr(flow, "ctx", self) is not self:
             raise ValueError("flow belongs to another context")
         flow = self.asdevice(flow)
-        if out is None:
-            out = [np.empty((H, W), pages[0].dtype) for _ in pages]
-        if len(out) != len(pages) or any(o.shape != (H, W) or o.dtype != pages[0].dtype or not o.flags.c_contiguous
-                                         or not o.flags.writeable for o in out):
-            raise ValueError("out must hold one writable C-contiguous array of the flow's (H, W) and the page dtype per page")
-        n = len(pages)
-        src = (C.c_void_p * n)(*[p.ctypes.data for p in pages])
-        dst = (C.c_void_p * n)(*[o.ctypes.data for o in out])
+        out, n, src, dst = self._page_pointers(pages, out, (H, W), "the flow's (H, W) and the page dtype")
         self._run(self.lib.ma_warp_affine_flow_pages_host, src, dst, n, _dt(pages[0].dtype), h, w, left, top, flow.ptr,
                   H, W, (C.c_double * 6)(*[float(v) for v in m]), interp)
         return out

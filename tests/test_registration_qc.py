@@ -104,8 +104,11 @@ def test_quality_maps_stay_out_of_the_measured_path_hash(tmp_path, monkeypatch):
     assert out == build.source_hash() and re.fullmatch(r"[0-9a-f]{16}", out)
     csrc = tmp_path / "csrc"
     shutil.copytree(build.CSRC, csrc)
-    headers = [str(csrc / "ma_internal.h"), str(tmp_path / "microaligner_hip.h")]
-    shutil.copy(os.path.join(ROOT, "include", "microaligner_hip.h"), headers[1])
+    # the same headers in the same order: those of csrc from the copy, the public one beside it
+    headers = [str((csrc if os.path.samefile(os.path.dirname(h), build.CSRC) else tmp_path) / os.path.basename(h))
+               for h in build.HEADERS]
+    assert str(csrc / "ma_internal.h") in headers and str(tmp_path / "microaligner_hip.h") in headers
+    shutil.copy(os.path.join(ROOT, "include", "microaligner_hip.h"), tmp_path / "microaligner_hip.h")
     monkeypatch.setattr(build, "CSRC", str(csrc))
     monkeypatch.setattr(build, "HEADERS", headers)
     assert build.source_hash() == out
