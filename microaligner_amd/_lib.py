@@ -163,6 +163,11 @@ COMPOSE_SIGNATURES = {
                                             C.POINTER(_d), _i]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_flowcompose.h (exact composition of two flows)
+FLOWCOMPOSE_SIGNATURES = {
+    "ma_compose_flows": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -177,7 +182,7 @@ def load():
             "microaligner_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + \
-            list(COMPOSE_SIGNATURES.items()):
+            list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

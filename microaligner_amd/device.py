@@ -763,6 +763,21 @@ class Context:
             self._run(self.lib.ma_merge_flows_tiled, flow1.ptr, flow2.ptr, H, W, int(tile), int(overlap), out.ptr)
         return out
 
+    def compose_flows(self, first, second):
+        """The flow of "warp by first, then warp the result by second": second + first sampled at (p - second), whole
+        image, replicate border (include/microaligner_flowcompose.h).  Device arrays in, a new device array out."""
+        for name, f in (("first", first), ("second", second)):
+            if f.dtype != np.float32 or len(f.shape) != 3 or f.shape[2] != 2:
+                raise ValueError(f"{name} must be an (H, W, 2) float32 flow, got {tuple(f.shape)} {f.dtype}")
+        if tuple(first.shape) != tuple(second.shape):
+            raise ValueError(f"flows must have the same shape, got {tuple(first.shape)} and {tuple(second.shape)}")
+        H, W = first.shape[:2]
+        if not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
+            raise ValueError(f"flow sides must be in [1, 2^24], got {(H, W)}")
+        out = self.empty((H, W, 2), np.float32)
+        self._run(self.lib.ma_compose_flows, first.ptr, second.ptr, H, W, out.ptr)
+        return out
+
     def pyr_down(self, img, minmax=False):
         h, w = img.shape
         out = self.empty(((h + 1) // 2, (w + 1) // 2), img.dtype)

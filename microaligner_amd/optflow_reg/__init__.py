@@ -1,3 +1,3 @@
 from .flow_calc import TileFlowCalc, farneback
-from .optflow_registrator import OptFlowRegistrator, merge_two_flows
+from .optflow_registrator import OptFlowRegistrator, compose_flows, merge_two_flows
 from .warper import Warper

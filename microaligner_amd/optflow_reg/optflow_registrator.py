@@ -8,6 +8,11 @@ array stays in HBM between the steps of a level and every step is a HIP kernel p
 (include/microaligner_hip.h).  The level loop reproduces the reference's accept/reject rules,
 including its quirks (Q1 absolute-coordinate flow merge, Q2 no x2 when upscaling to
 full resolution, Q3 x4 in the middle-level reject branch).
+
+Opt-in: OptFlowRegistrator.flow_composition = "exact" keeps every step of a level (pre-warp, dog, Farneback, gate) and
+replaces the bookkeeping of the flow between the levels by the exact composition of the per-level flows
+(compose_flows, include/microaligner_flowcompose.h) with a x2 at every upscale, the last one included: Q1-Q3 fixed
+together.  The default, "reference", leaves every call and every bit as it is.
 """
 from dataclasses import dataclass
 from math import log2
@@ -30,6 +35,21 @@ def merge_two_flows(flow1, flow2):
     f1, f2 = ctx.asdevice(flow1), ctx.asdevice(flow2)
     out = ctx.merge_flows(f1, f2, 0, 0)  # tile=0: the arrays themselves are the window
     return out if isinstance(flow1, DeviceArray) else out.numpy()
+
+
+def compose_flows(first, second):
+    """The flow of "warp by first, then warp the result by second", with warp(img, f)(p) = img(p - f(p)):
+    out(p) = second(p) + first sampled at (p - second(p)), linearly, first extended by its border values
+    (include/microaligner_flowcompose.h).  Both (H, W, 2) float32 of one shape; numpy in, numpy out; DeviceArray in,
+    DeviceArray out."""
+    for name, f in (("first", first), ("second", second)):
+        if getattr(f, "dtype", None) != np.float32 or len(f.shape) != 3 or f.shape[2] != 2:
+            raise ValueError(f"{name} must be an (H, W, 2) float32 flow")
+    if tuple(first.shape) != tuple(second.shape):
+        raise ValueError(f"flows must have the same shape, got {tuple(first.shape)} and {tuple(second.shape)}")
+    ctx = get_context()
+    out = ctx.compose_flows(ctx.asdevice(first), ctx.asdevice(second))
+    return out if isinstance(first, DeviceArray) else out.numpy()
 
 
 @dataclass
@@ -62,7 +82,14 @@ class OptFlowRegistrator:
         # here over the primitive entry points (the second implementation the tests compare the first with, and the one
         # that serves the two input classes the C entry point does not model: reference and moving image of different
         # dtypes, and float images whose max() is 0 without being all zero)
+        # (with flow_composition = "exact" the Python loop runs and engine has no further effect)
         self.engine = "c"
+        # "reference" (default): the reference's bookkeeping of the flow between the levels, quirks Q1-Q3 included, bit
+        # for bit.  "exact": the flow so far and a level's flow are composed exactly (compose_flows: the level's flow
+        # plus the flow so far sampled where the level's flow points, instead of the level's flow sampled at the
+        # absolute coordinate -flow, Q1), every upscale doubles the flow, the one to full size included (Q2), and a
+        # rejected level doubles it once, not twice (Q3).  The steps of a level and its gate are the same in both.
+        self.flow_composition = "reference"
         # True (default, the reference's behaviour): the mov_img GETTER returns the REFERENCE image, as the reference's does
         # (optflow_registrator.py:73-74, quirk Q4 -- nothing on the path reads it); False: it returns the moving image
         self.compat_mov_getter = True
@@ -120,6 +147,9 @@ class OptFlowRegistrator:
         check_img_is_provided(self._ref_img, "ref")
         check_img_is_provided(self._mov_img, "mov")
         check_img_dims_match(self._ref_img, self._mov_img)
+        if self.flow_composition not in ("reference", "exact"):
+            raise ValueError(f"unknown flow_composition {self.flow_composition!r}: 'reference' or 'exact'")
+        exact = self.flow_composition == "exact"
         device_in = isinstance(self._ref_img, DeviceArray) and isinstance(self._mov_img, DeviceArray)
         ctx = get_context()
         self._ctx = ctx
@@ -133,7 +163,7 @@ class OptFlowRegistrator:
             raise ValueError(f"unknown engine {self.engine!r}: 'c' or 'python'")
         reports = None
         # images of different dtypes (each keeps its own pyramid arithmetic, cv2 converts per input): the Python loop
-        if self.engine == "c" and ref_full.dtype == mov_full.dtype:
+        if self.engine == "c" and not exact and ref_full.dtype == mov_full.dtype:
             try:
                 result, reports = ctx.optflow_register(
                     ref_full, mov_full, self.num_pyr_lvl, self.num_iterations, self.tile_size, self.overlap,
@@ -183,8 +213,20 @@ class OptFlowRegistrator:
             self.level_reports.append(LevelReport(factor, tuple(ref_lvl.shape), float(after), float(before), accepted))
 
             nxt_hw = None if last else mov_pyr[lvl + 1].shape
-            if accepted:
-                self._log("    Better alignment than before")
+            self._log("    Better alignment than before" if accepted else "    Worse alignment than before")
+            if exact:
+                # total flow of this level: this level's flow after the flow so far, or the flow so far alone
+                if accepted:
+                    total = this_flow if lvl == 0 else ctx.compose_flows(m_flow, this_flow)
+                else:
+                    total = ctx.zeros(tuple(ref_lvl.shape) + (2,), np.float32) if lvl == 0 else m_flow
+                if not last:
+                    m_flow = ctx.pyr_up_flow(total, nxt_hw, 2.0)
+                elif self.use_full_res_img:
+                    m_flow = total
+                else:
+                    m_flow = ctx.pyr_up_flow(total, self._full_shape, 2.0)
+            elif accepted:
                 if lvl == 0:
                     m_flow = (ctx.pyr_up_flow(this_flow, nxt_hw, 2.0) if not last
                               else self._upscale_flow_to_full_res(this_flow, factor))
@@ -195,7 +237,6 @@ class OptFlowRegistrator:
                     else:
                         m_flow = ctx.pyr_up_flow(merged, nxt_hw, 2.0)
             else:
-                self._log("    Worse alignment than before")
                 if lvl == 0:
                     m_flow = ctx.zeros(tuple(nxt_hw if not last else self._full_shape) + (2,), np.float32)
                 elif last:

@@ -51,11 +51,20 @@ class RegParam:
     FIELDS = (("NumberPyramidLevels", int), ("NumberIterationsPerLevel", int), ("TileSize", int), ("Overlap", int),
               ("NumberOfWorkers", int), ("UseFullResImage", bool), ("UseDOG", bool))
 
-    def __init__(self, d):
+    def __init__(self, d, optflow=False):
         if not isinstance(d, dict):
             raise TypeError("registration parameters must be a mapping")
         for name, t in self.FIELDS:
             _check_dtype(name, t, d)
+        # addition, OptFlowReg only: OptFlowRegistrator.flow_composition, "reference" (also when absent) or "exact"
+        self.FlowComposition = None
+        if "FlowComposition" in d:
+            if not optflow:
+                raise ValueError("Field FlowComposition belongs to OptFlowReg only")
+            _check_dtype("FlowComposition", str, d)
+            if d["FlowComposition"] not in ("reference", "exact"):
+                raise ValueError(f"Field FlowComposition value is not one of: {['reference', 'exact']}")
+            self.FlowComposition = d["FlowComposition"]
         _check_min_max("NumberPyramidLevels", 0, 8, d)
         _check_min_max("NumberIterationsPerLevel", 1, None, d)
         _check_min_max("TileSize", 20, None, d)
@@ -69,7 +78,8 @@ class RegParam:
                     tile_size=self.TileSize, use_full_res_img=self.UseFullResImage, use_dog=self.UseDOG)
 
     def optflow_kwargs(self):
-        return dict(self.feature_kwargs(), overlap=self.Overlap)
+        extra = {} if self.FlowComposition is None else dict(flow_composition=self.FlowComposition)
+        return dict(self.feature_kwargs(), overlap=self.Overlap, **extra)
 
     def __repr__(self):
         return str(self.__dict__)
@@ -118,7 +128,7 @@ class PipelineConfig:
                              "FeatureReg or OptFlowReg must be present.")
         self.input_ome = None               # OME-XML description of the (first) input, passed through to the outputs
         self.feature = RegParam(reg["FeatureReg"]) if "FeatureReg" in reg else None
-        self.optflow = RegParam(reg["OptFlowReg"]) if "OptFlowReg" in reg else None
+        self.optflow = RegParam(reg["OptFlowReg"], optflow=True) if "OptFlowReg" in reg else None
 
 
 def read_config(path):
