@@ -8,10 +8,11 @@ Compute runs in hand-written HIP kernels for gfx950 behind a C-ABI (include/micr
 there is no CPU fallback.
 """
 from .feature_reg import FeatureRegistrator
-from .optflow_reg import OptFlowRegistrator, TileFlowCalc, Warper, farneback, compose_flows, merge_two_flows
+from .optflow_reg import OptFlowRegistrator, TileFlowCalc, Warper, farneback, compose_flows, merge_two_flows, \
+    invert_flow, transform_points
 from .shared_modules.registration_qc import FlowQC, RegistrationQC, assess_registration, flow_qc
 from .shared_modules.utils import max_project_and_normalize, pad_to_shape, transform_img_with_tmat
 
-__all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc", "farneback", "merge_two_flows", "compose_flows", "pad_to_shape",
+__all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc", "farneback", "merge_two_flows", "compose_flows", "invert_flow", "transform_points", "pad_to_shape",
            "transform_img_with_tmat", "max_project_and_normalize", "assess_registration", "flow_qc", "RegistrationQC", "FlowQC"]
 __version__ = "0.1.0"

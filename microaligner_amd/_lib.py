@@ -168,6 +168,14 @@ FLOWCOMPOSE_SIGNATURES = {
     "ma_compose_flows": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_flowinvert.h (dense inverse of a flow, points
+# between the registered and the moving frame)
+MA_POINTS_TO_MOVING, MA_POINTS_TO_REFERENCE = 0, 1   # enum ma_points_direction
+FLOWINVERT_SIGNATURES = {
+    "ma_invert_flow": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, C.POINTER(C.c_longlong)]),
+    "ma_transform_points": (_i, [_vp, _vp, _i, _vp, _i, _i, C.POINTER(_d), C.POINTER(_d), _i, _i, _i, _i, _d, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -182,7 +190,7 @@ def load():
             "microaligner_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + \
-            list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()):
+            list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()) + list(FLOWINVERT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
-           "flow_compose.hip"]
+           "flow_compose.hip", "flow_invert.hip"]
 HEADERS = [os.path.join(CSRC, "ma_internal.h"), os.path.join(CSRC, "remap_common.h"),
            os.path.join(HERE, "..", "include", "microaligner_hip.h")]
 # headers of single sources that are off the measured path (not in HEADERS, so not in source_hash())
@@ -23,7 +23,8 @@ _INTERP_HEADERS = [os.path.join(HERE, "..", "include", "microaligner_interp.h"),
 SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_qc.h")],
                   "remap_interp.hip": _INTERP_HEADERS,
                   "warp_compose.hip": _INTERP_HEADERS + [os.path.join(HERE, "..", "include", "microaligner_compose.h")],
-                  "flow_compose.hip": [os.path.join(HERE, "..", "include", "microaligner_flowcompose.h")]}
+                  "flow_compose.hip": [os.path.join(HERE, "..", "include", "microaligner_flowcompose.h")],
+                  "flow_invert.hip": [os.path.join(HERE, "..", "include", "microaligner_flowinvert.h")]}
 # -fno-slp-vectorize: the SLP vectoriser packs the sliding-window blur into v_pk_* ops with a storm of
 # register-pair shuffles (measured 1.65x slower on blur_h_solve, profiles/r01_*); packed math is written by hand
 # where it pays.
@@ -62,9 +63,11 @@ def source_hash():
     # pyramid, DOG, Farneback, warp, merge, NMI), the registration quality maps, which nothing on the path calls, and the
     # nearest / cubic / Lanczos-4 warps, which only a non-default Warper.interpolation reaches, and the one-resampling warp
     # through an affine matrix and a flow, which only a Warper.tmat reaches, and the page-warp driver, which holds no kernel
-    # and runs after the measured steps, and the exact flow composition, which only flow_composition="exact" reaches
+    # and runs after the measured steps, and the exact flow composition, which only flow_composition="exact" reaches, and
+    # the flow inverse and the point transforms, which only invert_flow() / transform_points() reach
     off_path = {"probe.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "affine.hip", "qc.hip",
-                "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip"}
+                "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
+                "flow_invert.hip"}
     for path in [os.path.join(CSRC, s) for s in SOURCES if s not in off_path] + HEADERS:
         h.update(open(path, "rb").read())
     h.update(" ".join(_flags()).encode())

@@ -63,6 +63,75 @@ def affine_flow_params(img_shape, img_dtype, flow_shape, flow_dtype, tmat, inter
     return interp, m, (W - w) // 2, (H - h) // 2
 
 
+POINT_DIRECTIONS = {"to_moving": L.MA_POINTS_TO_MOVING, "to_reference": L.MA_POINTS_TO_REFERENCE}
+
+
+def _check_flow(flow, name="flow"):
+    if getattr(flow, "dtype", None) != np.float32 or len(flow.shape) != 3 or flow.shape[2] != 2:
+        raise ValueError(f"{name} must be an (H, W, 2) float32 flow")
+    H, W = flow.shape[:2]
+    if not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
+        raise ValueError(f"flow sides must be in [1, 2^24], got {(H, W)}")
+    return int(H), int(W)
+
+
+def _check_iteration(max_iter, tol, tol_dtype):
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or not 1 <= int(max_iter) < 1 << 31:
+        raise ValueError(f"max_iter must be an integer in [1, 2^31), got {max_iter!r}")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)):
+        raise ValueError(f"tol must be a number, got {tol!r}")
+    with np.errstate(over="ignore"):
+        t = tol_dtype(tol)
+    if not (np.isfinite(t) and t >= 0):
+        raise ValueError(f"tol must be finite and not negative as {np.dtype(tol_dtype)}, got {tol!r}")
+    return int(max_iter), float(t)
+
+
+def invert_flow_params(flow, max_iter, tol):
+    """Checks of the dense flow inverse (include/microaligner_flowinvert.h) without touching a device:
+    (H, W, max_iter, tol as the float32 the kernel compares with).  ValueError for anything the C entry would refuse."""
+    H, W = _check_flow(flow)
+    return (H, W) + _check_iteration(max_iter, tol, np.float32)
+
+
+def transform_points_params(points, flow, direction, tmat, image_shape, max_iter, tol):
+    """Checks and host-side arguments of the point transforms (include/microaligner_flowinvert.h) without touching a
+    device: (points as a C-contiguous (N, 2) float64 array, direction code, the 6 doubles of the matrix that direction
+    uses or None, pad_left, pad_top, max_iter, tol).  tmat and image_shape are Warper.tmat and the shape of the moving
+    image it resamples (default: the flow's (H, W)); the matrix and the padding come from affine_flow_params.
+    ValueError for anything else."""
+    H, W = _check_flow(flow)
+    if not isinstance(direction, str) or direction not in POINT_DIRECTIONS:
+        raise ValueError(f"unknown direction {direction!r}: expected one of {sorted(POINT_DIRECTIONS)}")
+    if not isinstance(points, np.ndarray) or points.dtype != np.float64 or points.ndim != 2 or points.shape[1] != 2:
+        raise ValueError("points must be an (N, 2) float64 numpy array of (x, y)")
+    if points.shape[0] >= 1 << 31:
+        raise ValueError("at most 2^31 - 1 points per call")
+    max_iter, tol = _check_iteration(max_iter, tol, np.float64)
+    mat, left, top = None, 0, 0
+    if tmat is None:
+        if image_shape is not None:
+            raise ValueError("image_shape only has a meaning together with tmat")
+    else:
+        try:
+            shape = (H, W) if image_shape is None else tuple(int(v) for v in image_shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"image_shape must be (h, w), got {image_shape!r}") from None
+        _, m, left, top = affine_flow_params(shape, np.float32, flow.shape, flow.dtype, tmat)
+        mat = m if direction == "to_moving" else np.asarray(tmat, np.float64).ravel()
+    return np.ascontiguousarray(points), POINT_DIRECTIONS[direction], mat, left, top, max_iter, tol
+
+
+class InvertInfo(collections.namedtuple("InvertInfo", "not_converged residual")):
+    """invert_flow(..., return_info=True): the number of pixels that took max_iter steps without stopping, and the (H, W)
+    float32 size of every pixel's last step (NaN where it was NaN)."""
+
+
+class PointsInfo(collections.namedtuple("PointsInfo", "converged inside")):
+    """transform_points(..., return_info=True): per point, whether the iteration stopped (always True for "to_moving"
+    and a finite point), and whether the registered-frame coordinate lies inside the flow's grid."""
+
+
 class DeviceArray:
     """Dense row-major array living in HBM.  Freed back to the context's pool on `free()`/GC."""
 
@@ -777,6 +846,42 @@ class Context:
         out = self.empty((H, W, 2), np.float32)
         self._run(self.lib.ma_compose_flows, first.ptr, second.ptr, H, W, out.ptr)
         return out
+
+    def invert_flow(self, flow, max_iter=50, tol=1e-3, return_info=False):
+        """The inverse g of a flow f: g(q) = -f(q - g(q)), so that compose_flows(f, g) ~ 0, by a fixed-point iteration per
+        pixel in one kernel (include/microaligner_flowinvert.h).  A device array in, a new device array out; with
+        return_info an InvertInfo(not_converged, residual as a device array) beside it, at the cost of a synchronisation."""
+        H, W, max_iter, tol = invert_flow_params(flow, max_iter, tol)
+        out = self.empty((H, W, 2), np.float32)
+        if not return_info:
+            self._run(self.lib.ma_invert_flow, flow.ptr, H, W, max_iter, tol, out.ptr, None, None)
+            return out
+        residual, count = self.empty((H, W), np.float32), C.c_longlong(0)
+        self._run(self.lib.ma_invert_flow, flow.ptr, H, W, max_iter, tol, out.ptr, residual.ptr, C.byref(count))
+        return out, InvertInfo(int(count.value), residual)
+
+    def transform_points(self, points, flow, direction, tmat=None, image_shape=None, max_iter=50, tol=1e-4,
+                         return_info=False):
+        """(N, 2) float64 points (x, y) through a registration (include/microaligner_flowinvert.h): "to_moving" takes
+        points of the registered frame to the coordinate of the moving image that Warper samples there, "to_reference"
+        takes points of the moving image to the registered frame by solving p - flow(p) = tmat . point.  tmat / image_shape:
+        Warper.tmat and the shape of the moving image it resamples.  numpy points in and out; flow numpy or device
+        resident.  With return_info a PointsInfo(converged, inside) of bool arrays beside the points."""
+        pts, code, mat, left, top, max_iter, tol = transform_points_params(points, flow, direction, tmat, image_shape,
+                                                                           max_iter, tol)
+        flow = self.asdevice(flow)
+        n = pts.shape[0]
+        H, W = flow.shape[:2]
+        d_pts, d_conv, d_in = self._upload_raw(pts), self._raw(n), self._raw(n)
+        mat = None if mat is None else (C.c_double * 6)(*[float(v) for v in mat])
+        m6, t6 = (mat, None) if code == L.MA_POINTS_TO_MOVING else (None, mat)
+        self._run(self.lib.ma_transform_points, d_pts.ptr, n, flow.ptr, H, W, m6, t6, left, top, code, max_iter, tol,
+                  d_pts.ptr, d_conv.ptr, d_in.ptr)
+        out = self.download_raw(d_pts, (n, 2), np.float64)
+        if not return_info:
+            return out
+        return out, PointsInfo(self.download_raw(d_conv, (n,), np.uint8).astype(bool),
+                               self.download_raw(d_in, (n,), np.uint8).astype(bool))
 
     def pyr_down(self, img, minmax=False):
         h, w = img.shape

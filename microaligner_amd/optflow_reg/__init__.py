@@ -1,3 +1,4 @@
 from .flow_calc import TileFlowCalc, farneback
+from .flow_invert import invert_flow, transform_points
 from .optflow_registrator import OptFlowRegistrator, compose_flows, merge_two_flows
 from .warper import Warper
