@@ -176,6 +176,13 @@ FLOWINVERT_SIGNATURES = {
     "ma_transform_points": (_i, [_vp, _vp, _i, _vp, _i, _i, C.POINTER(_d), C.POINTER(_d), _i, _i, _i, _i, _d, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_residual.h (residual shift maps)
+MA_RESIDUAL_MAX_SHIFT, MA_RESIDUAL_MAX_CELL_PIXELS = 16, 1 << 23
+_residual_outputs = [C.POINTER(_d)] * 4 + [C.POINTER(C.c_ubyte)] * 2 + [C.POINTER(_d)]
+RESIDUAL_SIGNATURES = {
+    "ma_residual_shift_grid": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i] + _residual_outputs + _residual_outputs),
+}
+
 _lib = None
 
 
@@ -190,7 +197,8 @@ def load():
             "microaligner_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + \
-            list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()) + list(FLOWINVERT_SIGNATURES.items()):
+            list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()) + list(FLOWINVERT_SIGNATURES.items()) + \
+            list(RESIDUAL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
-           "flow_compose.hip", "flow_invert.hip"]
+           "flow_compose.hip", "flow_invert.hip", "residual_shift.hip"]
 HEADERS = [os.path.join(CSRC, "ma_internal.h"), os.path.join(CSRC, "remap_common.h"),
            os.path.join(HERE, "..", "include", "microaligner_hip.h")]
 # headers of single sources that are off the measured path (not in HEADERS, so not in source_hash())
@@ -24,7 +24,8 @@ SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_q
                   "remap_interp.hip": _INTERP_HEADERS,
                   "warp_compose.hip": _INTERP_HEADERS + [os.path.join(HERE, "..", "include", "microaligner_compose.h")],
                   "flow_compose.hip": [os.path.join(HERE, "..", "include", "microaligner_flowcompose.h")],
-                  "flow_invert.hip": [os.path.join(HERE, "..", "include", "microaligner_flowinvert.h")]}
+                  "flow_invert.hip": [os.path.join(HERE, "..", "include", "microaligner_flowinvert.h")],
+                  "residual_shift.hip": [os.path.join(HERE, "..", "include", "microaligner_residual.h")]}
 # -fno-slp-vectorize: the SLP vectoriser packs the sliding-window blur into v_pk_* ops with a storm of
 # register-pair shuffles (measured 1.65x slower on blur_h_solve, profiles/r01_*); packed math is written by hand
 # where it pays.
@@ -64,10 +65,11 @@ def source_hash():
     # nearest / cubic / Lanczos-4 warps, which only a non-default Warper.interpolation reaches, and the one-resampling warp
     # through an affine matrix and a flow, which only a Warper.tmat reaches, and the page-warp driver, which holds no kernel
     # and runs after the measured steps, and the exact flow composition, which only flow_composition="exact" reaches, and
-    # the flow inverse and the point transforms, which only invert_flow() / transform_points() reach
+    # the flow inverse and the point transforms, which only invert_flow() / transform_points() reach, and the residual shift
+    # maps, which only residual_shift() reaches
     off_path = {"probe.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "affine.hip", "qc.hip",
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
-                "flow_invert.hip"}
+                "flow_invert.hip", "residual_shift.hip"}
     for path in [os.path.join(CSRC, s) for s in SOURCES if s not in off_path] + HEADERS:
         h.update(open(path, "rb").read())
     h.update(" ".join(_flags()).encode())

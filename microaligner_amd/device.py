@@ -1013,6 +1013,38 @@ class Context:
                   folded.ctypes.data_as(pl), invalid.ctypes.data_as(pl), mean.ctypes.data_as(pd), mx.ctypes.data_as(pd))
         return jmin, folded, invalid, mean, mx
 
+    # residual shift maps (include/microaligner_residual.h) ------------------------------------------------------------
+    def residual_shift_grid(self, ref, b0, b1, cell_h, cell_w, max_shift, table=False):
+        """Per cell of the (cell_h, cell_w) grid: the ZNCC peak within +-max_shift px of the u8 labels (ref, b0) and, unless
+        b1 is None, (ref, b1).  -> (maps0, maps1), each a dict of (gy, gx) arrays shift_x, shift_y, score, score0 (float64),
+        at_limit, valid (bool) and table ((gy, gx, 2R + 1, 2R + 1) float64, or None without table=True); maps1 is None
+        without b1."""
+        for b in (b0, b1):
+            if b is not None and (ref.dtype != np.uint8 or b.dtype != np.uint8 or ref.shape != b.shape or ref.ndim != 2):
+                raise ValueError("residual shift labels must be 2-D uint8 arrays of equal shape")
+        h, w = ref.shape
+        R = int(max_shift)
+        gy, gx = -(-h // int(cell_h)), -(-w // int(cell_w))
+        pd, pb = C.POINTER(C.c_double), C.POINTER(C.c_ubyte)
+
+        def outputs(wanted):
+            if not wanted:
+                return None, [None] * 7
+            m = {k: np.empty((gy, gx)) for k in ("shift_x", "shift_y", "score", "score0")}
+            m["at_limit"], m["valid"] = np.empty((gy, gx), np.uint8), np.empty((gy, gx), np.uint8)
+            m["table"] = np.empty((gy, gx, 2 * R + 1, 2 * R + 1)) if table else None
+            return m, [m[k].ctypes.data_as(pd) for k in ("shift_x", "shift_y", "score", "score0")] + \
+                [m[k].ctypes.data_as(pb) for k in ("at_limit", "valid")] + \
+                [m["table"].ctypes.data_as(pd) if table else None]
+        m0, p0 = outputs(True)
+        m1, p1 = outputs(b1 is not None)
+        self._run(self.lib.ma_residual_shift_grid, ref.ptr, b0.ptr, b1.ptr if b1 is not None else None, h, w, int(cell_h),
+                  int(cell_w), R, *p0, *p1)
+        for m in (m0, m1):
+            if m is not None:
+                m["at_limit"], m["valid"] = m["at_limit"].astype(bool), m["valid"].astype(bool)
+        return m0, m1
+
     def max_project(self, stack):
         nz = stack.shape[0]
         out = self.empty(stack.shape[1:], stack.dtype)
