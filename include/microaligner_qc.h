@@ -16,7 +16,7 @@ extern "C" {
 #endif
 
 /* Per cell: sklearn normalized_mutual_info_score (arithmetic mean) of the u8 labels ref and b0, and of ref and b1 (b1 may
- * be NULL: nmi1 / ncc1 are then not written), stated as the gate's ma_nmi_u8 states it (same doubles as ma_nmi_u8 on the
+ * be NULL: nmi1 / ncc1 are then not written), computed by the gate's own code (same doubles as ma_nmi_u8 on the
  * cropped cell), and the Pearson correlation of the same labels from the exact integer moments of the joint histogram
  * (NaN where either label set is constant).  Every cell must hold fewer than 2^32 pixels. */
 int ma_qc_nmi_grid(ma_ctx* ctx, const uint8_t* ref, const uint8_t* b0, const uint8_t* b1, int h, int w, int cell_h, int cell_w,

@@ -16,16 +16,17 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
            "flow_compose.hip", "flow_invert.hip", "residual_shift.hip"]
-HEADERS = [os.path.join(CSRC, "ma_internal.h"), os.path.join(CSRC, "remap_common.h"),
+HEADERS = [os.path.join(CSRC, "ma_internal.h"), os.path.join(CSRC, "remap_common.h"), os.path.join(CSRC, "nmi_score.h"),
            os.path.join(HERE, "..", "include", "microaligner_hip.h")]
 # headers of single sources that are off the measured path (not in HEADERS, so not in source_hash())
 _INTERP_HEADERS = [os.path.join(HERE, "..", "include", "microaligner_interp.h"), os.path.join(CSRC, "remap_interp.h")]
-SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_qc.h")],
+_CELL_GRID = os.path.join(CSRC, "cell_grid.h")
+SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_qc.h"), _CELL_GRID],
                   "remap_interp.hip": _INTERP_HEADERS,
                   "warp_compose.hip": _INTERP_HEADERS + [os.path.join(HERE, "..", "include", "microaligner_compose.h")],
                   "flow_compose.hip": [os.path.join(HERE, "..", "include", "microaligner_flowcompose.h")],
                   "flow_invert.hip": [os.path.join(HERE, "..", "include", "microaligner_flowinvert.h")],
-                  "residual_shift.hip": [os.path.join(HERE, "..", "include", "microaligner_residual.h")]}
+                  "residual_shift.hip": [os.path.join(HERE, "..", "include", "microaligner_residual.h"), _CELL_GRID]}
 # -fno-slp-vectorize: the SLP vectoriser packs the sliding-window blur into v_pk_* ops with a storm of
 # register-pair shuffles (measured 1.65x slower on blur_h_solve, profiles/r01_*); packed math is written by hand
 # where it pays.
@@ -59,14 +60,18 @@ def source_hash():
     import hashlib
     h = hashlib.sha256()
     # register.hip decides which launches the measured path makes and on which stream, ma_api.hip how the buffer cache and
-    # the streams behave: both are part of what a profile measures.  Left out: the clock probe and the feature stage
-    # (FAST / DAISY / 2-NN / affine warp), which has its own tests and timings and no kernel on the measured path (cfg3:
-    # pyramid, DOG, Farneback, warp, merge, NMI), the registration quality maps, which nothing on the path calls, and the
-    # nearest / cubic / Lanczos-4 warps, which only a non-default Warper.interpolation reaches, and the one-resampling warp
-    # through an affine matrix and a flow, which only a Warper.tmat reaches, and the page-warp driver, which holds no kernel
-    # and runs after the measured steps, and the exact flow composition, which only flow_composition="exact" reaches, and
-    # the flow inverse and the point transforms, which only invert_flow() / transform_points() reach, and the residual shift
-    # maps, which only residual_shift() reaches
+    # the streams behave: both are part of what a profile measures.  nmi_score.h holds the gate's score (HEADERS).
+    # Left out, having no kernel on the measured path (cfg3: pyramid, DOG, Farneback, warp, merge, NMI):
+    #   - the clock probe;
+    #   - the feature stage (FAST / DAISY / 2-NN / affine warp), which has its own tests and timings;
+    #   - the registration quality maps, which nothing on the path calls;
+    #   - the nearest / cubic / Lanczos-4 warps, which only a non-default Warper.interpolation reaches;
+    #   - the one-resampling warp through an affine matrix and a flow, which only a Warper.tmat reaches;
+    #   - the page-warp driver, which holds no kernel and runs after the measured steps;
+    #   - the exact flow composition, which only flow_composition="exact" reaches;
+    #   - the flow inverse and the point transforms, which only invert_flow() / transform_points() reach;
+    #   - the residual shift maps, which only residual_shift() reaches;
+    #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps (SOURCE_HEADERS).
     off_path = {"probe.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "affine.hip", "qc.hip",
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
                 "flow_invert.hip", "residual_shift.hip"}

@@ -3,22 +3,19 @@
 // Labels are pixel values, so the contingency matrix is a 256x256 joint histogram (exact integer
 // counts); the score follows sklearn's formula in f64.
 #include "ma_internal.h"
+#include "nmi_score.h"
 
-#include <cfloat>
 #include <cstdlib>
 
 namespace {
 
 // Joint histogram with LDS privatisation, one pass over the pixels.  grid: (pixel slices, chunks).  A block holds the
-// whole 256 x 256 joint histogram of its slice in LDS as 16-bit counters packed two to a word (128 KiB): a slice has
-// at most 65 520 pixels, so no counter can reach 2^16 and a plain 32-bit LDS atomic add of 1 << 16 * (bin & 1) never
-// carries into its neighbour.  Every pixel is read and decoded once (2 B/px of HBM traffic = the algorithmic bytes;
-// the round-1 kernel kept 32-bit counters for a quarter of the labels and read every slice four times); then the
-// non-zero counters are added to the chunk's histogram in HBM.  Lanes read 16 consecutive pixels each (one 16-byte
+// whole 256 x 256 joint histogram of its slice in LDS as the packed 16-bit counters of nmi_score.h (128 KiB).  Every pixel
+// is read and decoded once (2 B/px of HBM traffic = the algorithmic bytes; the round-1 kernel kept 32-bit counters for a
+// quarter of the labels and read every slice four times); then the non-zero counters are added to the chunk's histogram in HBM.  Lanes read 16 consecutive pixels each (one 16-byte
 // load per array) so that the 64 lanes of an LDS-atomic instruction hit pixels 16 apart, which decorrelates the bins
 // on smooth DOG images.  Measured alternatives (profiles/r02_notes.md): two label bands of 32-bit counters 0.167 ms
 // per launch, this kernel 0.171, the four-band kernel 0.281.
-constexpr int HIST_SLICE16 = 65520;
 // blockIdx.z selects the second label image (b0 or b1: the "after" and the "before" half of the gate share `a` and one
 // launch); its histograms follow those of b0.
 // NB > 1: the labels of `a` are cut into NB bands and a block counts one band of its slice (blockIdx.z = image * NB + band):
@@ -41,15 +38,14 @@ __global__ __launch_bounds__(NT) void joint_hist16_kernel(const uint8_t* __restr
     size_t s0 = c0 + (size_t)blockIdx.x * HIST_SLICE16;
     const size_t s1 = s0 + HIST_SLICE16 < c1 ? s0 + HIST_SLICE16 : c1;
     if (s0 >= s1) return;
-    for (int i = threadIdx.x; i < WORDS; i += NT) h[i] = 0;
+    hist16_zero<NT, WORDS>(h);
     __syncthreads();
     auto count = [&](unsigned ai, unsigned bi) {
         if (NB > 1) {
             ai -= band * BAND;
             if (ai >= (unsigned)BAND) return;
         }
-        const unsigned bin = ai * 256u + bi;
-        atomicAdd(&h[bin >> 1], 1u << ((bin & 1u) * 16u));
+        hist16_add(h, ai, bi);
     };
     size_t al = (s0 + 15) & ~(size_t)15;
     if (al > s1) al = s1;
@@ -67,118 +63,23 @@ __global__ __launch_bounds__(NT) void joint_hist16_kernel(const uint8_t* __restr
     }
     for (size_t i = al + nvec * 16 + threadIdx.x; i < s1; i += NT) count(a[i], b[i]);
     __syncthreads();
-    unsigned* hh = hist + ((size_t)img * gridDim.y + blockIdx.y) * 65536 + (size_t)band * (2 * WORDS);
-    for (int i = threadIdx.x; i < WORDS; i += NT) {
-        const unsigned c = h[i];
-        if (c & 0xffffu) atomicAdd(&hh[2 * i], c & 0xffffu);
-        if (c >> 16) atomicAdd(&hh[2 * i + 1], c >> 16);
-    }
+    hist16_flush<NT, WORDS>(h, hist + ((size_t)img * gridDim.y + blockIdx.y) * 65536 + (size_t)band * (2 * WORDS));
 }
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
-// Four blocks of 256 threads per chunk histogram (blockIdx.y = q): thread j of block q owns column j of the rows [64q, 64q+64),
-// so the 2 x 65536 double-precision logarithms of a chunk are spread over 16 waves -- as in the single block of 1024 threads of
-// rounds 1 - 5, whose placement needed sixteen free wave slots on ONE CU at once and waited 380 us on average (107 alone) for
-// the companion stream's dog() blocks to leave (profiles/r06_kernel_stats_cfg3_companion_on.csv).  Each wave leaves its partial
-// sums in `part`; nmi_final_kernel adds them in the order the single block used (wave 0 .. 15), so the scores keep their bits.
-constexpr int NR_T = 256, NR_Q = 4;
-// per histogram: [0..15] mutual-information partials (wave 4q + w), [16..19] / [20..23] entropy partials of a / b (the waves of
-// block 0), [24..27] / [28..31] number of non-empty labels of a among the block's rows / of b (block 0 only counts them)
-constexpr int NR_PART = 32;
 // block (b, q): histogram b, chunk b % nchunks (the histograms of a second label image follow those of the first)
 __global__ __launch_bounds__(NR_T) void nmi_reduce_kernel(const unsigned* __restrict__ hist, size_t n, size_t chunk,
                                                           unsigned nchunks, double* __restrict__ part)
 {
-    __shared__ unsigned pa[64], pb[256];
-    __shared__ int cnt[2];
-    const unsigned* hh = hist + (size_t)blockIdx.x * 65536;
-    const int j = threadIdx.x, q = blockIdx.y, lane = j & 63, w = j >> 6;
     const size_t c0 = (size_t)(blockIdx.x % nchunks) * chunk;
     const double N = (double)((c0 + chunk < n ? c0 + chunk : n) - c0);
-    double* out = part + (size_t)blockIdx.x * NR_PART;
-
-    if (j < 2) cnt[j] = 0;
-    // marginals (counts < 2^32 by the chunk limit): column j over ALL rows (coalesced across the wave), and -- threads 0 .. 63 --
-    // row 64 q + j (64 independent 16-byte loads)
-    {
-        unsigned sb = 0;
-#pragma unroll 16
-        for (int r = 0; r < 256; r++) sb += hh[r * 256 + j];
-        pb[j] = sb;
-        if (j < 64) {
-            const uint4* row = reinterpret_cast<const uint4*>(hh + (64 * q + j) * 256);
-            unsigned sa = 0;
-#pragma unroll 16
-            for (int k = 0; k < 64; k++) { uint4 v = row[k]; sa += v.x + v.y + v.z + v.w; }
-            pa[j] = sa;
-        }
-    }
-    __syncthreads();
-    if (j < 64 && pa[j] > 0) atomicAdd(&cnt[0], 1);
-    if (q == 0 && pb[j] > 0) atomicAdd(&cnt[1], 1);
-    __syncthreads();
-    const double logN = log(N);
-    const unsigned long long pbj = pb[j];
-    double mi = 0.0;
-    if (pbj > 0) {
-#pragma unroll 8
-        for (int rr = 0; rr < 64; rr++) {
-            unsigned nij = hh[(64 * q + rr) * 256 + j];
-            if (nij) {
-                double log_nm = log((double)nij);
-                double nm = (double)nij / N;
-                double outer = (double)((long long)pa[rr] * (long long)pbj);
-                double log_outer = -log(outer) + logN + logN;
-                double term = nm * (log_nm - logN) + nm * log_outer;
-                if (fabs(term) < DBL_EPSILON) term = 0.0;
-                mi += term;
-            }
-        }
-    }
-    mi = wave_sum(mi);
-    if (lane == 0) out[4 * q + w] = mi;
-    // entropies: label j of a is row j of the histogram -- block j / 64 holds its marginal (thread j % 64); label j of b: block 0
-    double ha = 0.0, hb = 0.0;
-    if (j < 64 && pa[j] > 0) ha = ((double)pa[j] / N) * (log((double)pa[j]) - logN);
-    if (q == 0 && pbj > 0) hb = ((double)pbj / N) * (log((double)pbj) - logN);
-    // the single block summed ha over its waves 0 .. 3 = labels 0 .. 255 in runs of 64: here run q is wave 0 of block q
-    ha = wave_sum(ha);
-    hb = wave_sum(hb);
-    if (lane == 0) {
-        if (w == 0) out[16 + q] = ha;
-        if (q == 0) out[20 + w] = hb;
-    }
-    if (j == 0) {
-        out[24 + q] = (double)cnt[0];
-        if (q == 0) out[28] = (double)cnt[1];
-    }
+    nmi_reduce_block<false>(hist + (size_t)blockIdx.x * 65536, N, part + (size_t)blockIdx.x * NR_PART, nullptr);
 }
 
 __global__ __launch_bounds__(64) void nmi_final_kernel(const double* __restrict__ part, unsigned nhist, double* __restrict__ scores)
 {
     const unsigned b = blockIdx.x * 64 + threadIdx.x;
     if (b >= nhist) return;
-    const double* p = part + (size_t)b * NR_PART;
-    const int ca = (int)(p[24] + p[25] + p[26] + p[27]), cb = (int)p[28];
-    if (ca == 1 && cb == 1) { scores[b] = 1.0; return; }      // both label sets have a single value
-    double tot[3] = {0.0, 0.0, 0.0};
-    for (int i = 0; i < 16; i++) tot[0] += p[i];
-    for (int i = 0; i < 4; i++) { tot[1] += p[16 + i]; tot[2] += p[20 + i]; }
-    double m = tot[0] < 0 ? 0.0 : tot[0];
-    double score;
-    if (fabs(m) < DBL_EPSILON) score = 0.0;
-    else {
-        double h_a = ca == 1 ? 0.0 : -tot[1], h_b = cb == 1 ? 0.0 : -tot[2];
-        double norm = 0.5 * (h_a + h_b);
-        if (norm < DBL_EPSILON) norm = DBL_EPSILON;
-        score = m / norm;
-    }
-    scores[b] = score;
+    scores[b] = nmi_final_score(part + (size_t)b * NR_PART);
 }
 
 } // namespace

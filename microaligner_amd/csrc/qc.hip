@@ -1,64 +1,44 @@
 // Registration quality maps (include/microaligner_qc.h): per-cell NMI / NCC of label images against a reference, and
 // per-cell Jacobian and magnitude statistics of a flow.  Off the measured path: nothing in register() or warp() calls it.
 //
-// The NMI of a cell is the gate's score (nmi.hip) of the cell's pixels: the same 256 x 256 joint histogram, the same f64
-// formula in the same reduction order, so a cell gives the bits ma_nmi_u8 gives for the cropped cell.  nmi.hip is part of
-// the measured path's source hash and is left untouched; the score arithmetic is stated again below, and the tests hold
-// the two statements to bit equality.
-#include "ma_internal.h"
+// The NMI of a cell is the gate's score of the cell's pixels, computed by the gate's own code (nmi_score.h): the same
+// 256 x 256 joint histogram, the same f64 formula in the same reduction order, so a cell gives the bits ma_nmi_u8 gives for
+// the cropped cell.
+#include "cell_grid.h"
+#include "nmi_score.h"
 #include "../../include/microaligner_qc.h"
 
-#include <cfloat>
 #include <cmath>
 
 namespace {
 
-// ---- cell geometry ------------------------------------------------------------------------------------------------
-struct QcCells {
-    int h, w, ch, cw, gx;
-    long long cell0;   // first cell of the batch (row-major cell index)
-};
-
-__device__ __forceinline__ void qc_cell_rect(const QcCells& g, long long cell, int& y0, int& y1, int& x0, int& x1)
-{
-    const int ci = (int)(cell / g.gx), cj = (int)(cell % g.gx);
-    y0 = ci * g.ch;
-    y1 = min(y0 + g.ch, g.h);
-    x0 = cj * g.cw;
-    x1 = min(x0 + g.cw, g.w);
-}
-
 // ---- joint histograms of 2-D cells ----------------------------------------------------------------------------------
-// As joint_hist16_kernel (nmi.hip): a block holds the 256 x 256 histogram of one slice in LDS as 16-bit counters packed two
-// to a word (128 KiB); a slice has at most 65 520 pixels, so no counter carries into its neighbour.  Here a slice is a
-// rectangle of a cell: the cell's columns are cut into n_seg segments of at most seg_w <= 65 520 columns (rows wider than
-// a slice), each segment into runs of rows_per = 65 520 / seg_w rows.  blockIdx.x = slice (segment + n_seg * row run),
-// blockIdx.y = cell of the batch, blockIdx.z = label image (b0 / b1, sharing `a`).  Slices of the geometry of a full cell
-// that fall outside a ragged cell are empty.  Work items are 16-byte blocks of the image memory within one row of the
-// slice, so a lane reads 16 consecutive pixels with one 16-byte load per array where the block lies wholly inside the
-// row (decorrelating the bins of neighbouring lanes on smooth images, as in nmi.hip) and byte by byte at the row ends.
-constexpr int QC_SLICE = 65520;
+// A block holds the 256 x 256 histogram of one slice in LDS as the packed 16-bit counters of nmi_score.h (128 KiB), a
+// slice of at most HIST_SLICE16 pixels.  Here a slice is a rectangle of a cell: the cell's columns are cut into n_seg
+// segments of at most seg_w <= HIST_SLICE16 columns (rows wider than a slice), each segment into runs of
+// rows_per = HIST_SLICE16 / seg_w rows.  blockIdx.x = slice (segment + n_seg * row run), blockIdx.y = cell of the batch,
+// blockIdx.z = label image (b0 / b1, sharing `a`).  Slices of the geometry of a full cell that fall outside a ragged cell
+// are empty.  Work items are 16-byte blocks of the image memory within one row of the slice, so a lane reads 16
+// consecutive pixels with one 16-byte load per array where the block lies wholly inside the row (decorrelating the bins of
+// neighbouring lanes on smooth images, as in nmi.hip) and byte by byte at the row ends.
 constexpr long long QC_BATCH = 2048;
 
 template <int NT>
 __global__ __launch_bounds__(NT) void qc_joint_hist_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b0,
-                                                           const uint8_t* __restrict__ b1, QcCells g, int seg_w, int n_seg,
+                                                           const uint8_t* __restrict__ b1, MaCellGrid g, int seg_w, int n_seg,
                                                            int rows_per, int vec_ok, unsigned* __restrict__ hist)
 {
     extern __shared__ unsigned h[];              // [256 * 256 / 2]
     const uint8_t* __restrict__ b = blockIdx.z ? b1 : b0;
     int cy0, cy1, cx0, cx1;
-    qc_cell_rect(g, g.cell0 + blockIdx.y, cy0, cy1, cx0, cx1);
+    g.rect(g.cell0 + blockIdx.y, cy0, cy1, cx0, cx1);
     const int seg = blockIdx.x % n_seg, rs = blockIdx.x / n_seg;
     const int x0 = cx0 + seg * seg_w, y0 = cy0 + rs * rows_per;
     if (x0 >= cx1 || y0 >= cy1) return;
     const int x1 = min(x0 + seg_w, cx1), y1 = min(y0 + rows_per, cy1);
-    for (int i = threadIdx.x; i < 32768; i += NT) h[i] = 0;
+    hist16_zero<NT, 32768>(h);
     __syncthreads();
-    auto count = [&](unsigned ai, unsigned bi) {
-        const unsigned bin = ai * 256u + bi;
-        atomicAdd(&h[bin >> 1], 1u << ((bin & 1u) * 16u));
-    };
+    auto count = [&](unsigned ai, unsigned bi) { hist16_add(h, ai, bi); };
     const int nbm = (x1 - x0 + 15) / 16 + 1;    // 16-byte blocks a row of the slice touches, at most
     const int items = (y1 - y0) * nbm;
     for (int t = threadIdx.x; t < items; t += NT) {
@@ -79,137 +59,34 @@ __global__ __launch_bounds__(NT) void qc_joint_hist_kernel(const uint8_t* __rest
         }
     }
     __syncthreads();
-    unsigned* hh = hist + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * 65536;
-    for (int i = threadIdx.x; i < 32768; i += NT) {
-        const unsigned c = h[i];
-        if (c & 0xffffu) atomicAdd(&hh[2 * i], c & 0xffffu);
-        if (c >> 16) atomicAdd(&hh[2 * i + 1], c >> 16);
-    }
+    hist16_flush<NT, 32768>(h, hist + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * 65536);
 }
 
-__device__ __forceinline__ double qc_wave_sum(double v)
+// The gate's score per cell (nmi_reduce_block): N is the cell's number of pixels; besides the wave partials each block leaves
+// the integer moments of its rows for the Pearson correlation.
+__global__ __launch_bounds__(NR_T) void qc_score_reduce_kernel(const unsigned* __restrict__ hist, MaCellGrid g, unsigned ncells,
+                                                               double* __restrict__ part, unsigned long long* __restrict__ mom)
 {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
-// The gate's per-chunk score (nmi_reduce_kernel + nmi_final_kernel of nmi.hip) stated again, per cell: four blocks of 256
-// threads per histogram, thread j of block q owns column j of the rows [64q, 64q + 64); each wave leaves its partial sums in
-// `part`, the final kernel adds them in the order wave 0 .. 15.  Besides, each block adds the exact integer moments of its
-// rows (sum a, sum a^2, sum ab; block 0 also sum b, sum b^2) for the Pearson correlation.
-constexpr int QC_RT = 256, QC_RQ = 4, QC_PART = 32, QC_MOM = 5;
-__global__ __launch_bounds__(QC_RT) void qc_score_reduce_kernel(const unsigned* __restrict__ hist, QcCells g, unsigned ncells,
-                                                                double* __restrict__ part, unsigned long long* __restrict__ mom)
-{
-    __shared__ unsigned pa[64], pb[256];
-    __shared__ int cnt[2];
-    __shared__ unsigned long long sm[QC_MOM];
-    const unsigned* hh = hist + (size_t)blockIdx.x * 65536;
-    const int j = threadIdx.x, q = blockIdx.y, lane = j & 63, w = j >> 6;
     int cy0, cy1, cx0, cx1;
-    qc_cell_rect(g, g.cell0 + blockIdx.x % ncells, cy0, cy1, cx0, cx1);
+    g.rect(g.cell0 + blockIdx.x % ncells, cy0, cy1, cx0, cx1);
     const double N = (double)((size_t)(cy1 - cy0) * (size_t)(cx1 - cx0));
-    double* out = part + (size_t)blockIdx.x * QC_PART;
-
-    if (j < 2) cnt[j] = 0;
-    if (j < QC_MOM) sm[j] = 0;
-    {
-        unsigned sb = 0;
-#pragma unroll 16
-        for (int r = 0; r < 256; r++) sb += hh[r * 256 + j];
-        pb[j] = sb;
-        if (j < 64) {
-            const uint4* row = reinterpret_cast<const uint4*>(hh + (64 * q + j) * 256);
-            unsigned sa = 0;
-#pragma unroll 16
-            for (int k = 0; k < 64; k++) { uint4 v = row[k]; sa += v.x + v.y + v.z + v.w; }
-            pa[j] = sa;
-        }
-    }
-    __syncthreads();
-    if (j < 64 && pa[j] > 0) atomicAdd(&cnt[0], 1);
-    if (q == 0 && pb[j] > 0) atomicAdd(&cnt[1], 1);
-    __syncthreads();
-    const double logN = log(N);
-    const unsigned long long pbj = pb[j];
-    double mi = 0.0;
-    unsigned long long sab = 0;
-    if (pbj > 0) {
-#pragma unroll 8
-        for (int rr = 0; rr < 64; rr++) {
-            unsigned nij = hh[(64 * q + rr) * 256 + j];
-            if (nij) {
-                double log_nm = log((double)nij);
-                double nm = (double)nij / N;
-                double outer = (double)((long long)pa[rr] * (long long)pbj);
-                double log_outer = -log(outer) + logN + logN;
-                double term = nm * (log_nm - logN) + nm * log_outer;
-                if (fabs(term) < DBL_EPSILON) term = 0.0;
-                mi += term;
-                sab += (unsigned long long)(64 * q + rr) * (unsigned long long)nij;
-            }
-        }
-    }
-    mi = qc_wave_sum(mi);
-    if (lane == 0) out[4 * q + w] = mi;
-    double ha = 0.0, hb = 0.0;
-    if (j < 64 && pa[j] > 0) ha = ((double)pa[j] / N) * (log((double)pa[j]) - logN);
-    if (q == 0 && pbj > 0) hb = ((double)pbj / N) * (log((double)pbj) - logN);
-    ha = qc_wave_sum(ha);
-    hb = qc_wave_sum(hb);
-    if (lane == 0) {
-        if (w == 0) out[16 + q] = ha;
-        if (q == 0) out[20 + w] = hb;
-    }
-    if (j == 0) {
-        out[24 + q] = (double)cnt[0];
-        if (q == 0) out[28] = (double)cnt[1];
-    }
-    // integer moments (exact: every sum is < 2^32 * 255^2 < 2^48)
-    if (sab) atomicAdd(&sm[2], sab * (unsigned long long)j);
-    if (j < 64 && pa[j] > 0) {
-        const unsigned long long ai = 64 * q + j;
-        atomicAdd(&sm[0], ai * pa[j]);
-        atomicAdd(&sm[1], ai * ai * pa[j]);
-    }
-    if (q == 0 && pbj > 0) {
-        atomicAdd(&sm[3], (unsigned long long)j * pbj);
-        atomicAdd(&sm[4], (unsigned long long)j * j * pbj);
-    }
-    __syncthreads();
-    if (j < QC_MOM) mom[((size_t)blockIdx.x * QC_RQ + q) * QC_MOM + j] = sm[j];
+    nmi_reduce_block<true>(hist + (size_t)blockIdx.x * 65536, N, part + (size_t)blockIdx.x * NR_PART,
+                           mom + ((size_t)blockIdx.x * NR_Q + blockIdx.y) * NR_MOM);
 }
 
 // scores[b] = NMI, scores[nhist + b] = Pearson r of histogram b
 __global__ __launch_bounds__(64) void qc_score_final_kernel(const double* __restrict__ part, const unsigned long long* __restrict__ mom,
-                                                            QcCells g, unsigned ncells, unsigned nhist, double* __restrict__ scores)
+                                                            MaCellGrid g, unsigned ncells, unsigned nhist, double* __restrict__ scores)
 {
     const unsigned b = blockIdx.x * 64 + threadIdx.x;
     if (b >= nhist) return;
-    const double* p = part + (size_t)b * QC_PART;
-    const int ca = (int)(p[24] + p[25] + p[26] + p[27]), cb = (int)p[28];
-    double score;
-    if (ca == 1 && cb == 1) score = 1.0;
-    else {
-        double tot[3] = {0.0, 0.0, 0.0};
-        for (int i = 0; i < 16; i++) tot[0] += p[i];
-        for (int i = 0; i < 4; i++) { tot[1] += p[16 + i]; tot[2] += p[20 + i]; }
-        double m = tot[0] < 0 ? 0.0 : tot[0];
-        if (fabs(m) < DBL_EPSILON) score = 0.0;
-        else {
-            double h_a = ca == 1 ? 0.0 : -tot[1], h_b = cb == 1 ? 0.0 : -tot[2];
-            double norm = 0.5 * (h_a + h_b);
-            if (norm < DBL_EPSILON) norm = DBL_EPSILON;
-            score = m / norm;
-        }
-    }
-    scores[b] = score;
+    scores[b] = nmi_final_score(part + (size_t)b * NR_PART);
 
-    unsigned long long s[QC_MOM] = {0, 0, 0, 0, 0};
-    for (int q = 0; q < QC_RQ; q++)
-        for (int k = 0; k < QC_MOM; k++) s[k] += mom[((size_t)b * QC_RQ + q) * QC_MOM + k];
+    unsigned long long s[NR_MOM] = {0, 0, 0, 0, 0};
+    for (int q = 0; q < NR_Q; q++)
+        for (int k = 0; k < NR_MOM; k++) s[k] += mom[((size_t)b * NR_Q + q) * NR_MOM + k];
     int cy0, cy1, cx0, cx1;
-    qc_cell_rect(g, g.cell0 + b % ncells, cy0, cy1, cx0, cx1);
+    g.rect(g.cell0 + b % ncells, cy0, cy1, cx0, cx1);
     const __int128 n = (__int128)((long long)(cy1 - cy0) * (long long)(cx1 - cx0));
     const __int128 sa = s[0], saa = s[1], sab = s[2], sb = s[3], sbb = s[4];
     const __int128 cov = n * sab - sa * sb, va = n * saa - sa * sa, vb = n * sbb - sb * sb;
@@ -235,8 +112,6 @@ struct QcFlowPart {
     unsigned folded, invalid, nfin, pad;
 };
 
-__device__ __forceinline__ bool qc_finite(double x) { return x - x == 0.0; }
-
 template <int NT>
 __device__ __forceinline__ void qc_block_combine(QcFlowPart* s, QcFlowPart v)
 {
@@ -258,13 +133,13 @@ __device__ __forceinline__ void qc_block_combine(QcFlowPart* s, QcFlowPart v)
     }
 }
 
-__global__ __launch_bounds__(QF_T) void qc_flow_tile_kernel(const float* __restrict__ flow, QcCells g, int ntx, int ntiles,
+__global__ __launch_bounds__(QF_T) void qc_flow_tile_kernel(const float* __restrict__ flow, MaCellGrid g, int ntx, int ntiles,
                                                             int vec_ok, QcFlowPart* __restrict__ part)
 {
     __shared__ float su[4][QF_LW], sv[4][QF_LW];
     __shared__ QcFlowPart red[QF_T];
     int cy0, cy1, cx0, cx1;
-    qc_cell_rect(g, g.cell0 + blockIdx.y, cy0, cy1, cx0, cx1);
+    g.rect(g.cell0 + blockIdx.y, cy0, cy1, cx0, cx1);
     const int tx = blockIdx.x % ntx, ty = blockIdx.x / ntx;
     const int x0 = cx0 + tx * QF_TW, y0 = cy0 + ty * QF_TH;
     QcFlowPart* out = part + (size_t)blockIdx.y * ntiles + blockIdx.x;
@@ -330,11 +205,11 @@ __global__ __launch_bounds__(QF_T) void qc_flow_tile_kernel(const float* __restr
             const double det = __dsub_rn(__dmul_rn(__dadd_rn(1.0, dudx), __dadd_rn(1.0, dvdy)), __dmul_rn(dudy, dvdx));
             // det is finite exactly when every value its stencil reads is: finite f32 values give finite differences and
             // products in f64, and a non-finite operand of +, -, * never yields a finite result
-            if (qc_finite(det)) {
+            if (ma_finite(det)) {
                 acc.jmin = fmin(acc.jmin, det);
                 acc.folded += det <= 0.0;
             }
-            if (qc_finite(u) && qc_finite(v)) {
+            if (ma_finite(u) && ma_finite(v)) {
                 const double m = __dsqrt_rn(__dadd_rn(__dmul_rn(u, u), __dmul_rn(v, v)));
                 acc.sum = __dadd_rn(acc.sum, m);
                 acc.max = fmax(acc.max, m);
@@ -386,15 +261,6 @@ __global__ __launch_bounds__(QF_RT) void qc_flow_cell_kernel(const QcFlowPart* _
     }
 }
 
-int qc_grid(int h, int w, int cell_h, int cell_w, long long* ncells, int* gx)
-{
-    MA_REQUIRE(h > 0 && w > 0, "empty image");
-    MA_REQUIRE(cell_h > 0 && cell_w > 0, "cell size must be >= 1");
-    *gx = (w + cell_w - 1) / cell_w;
-    *ncells = (long long)((h + cell_h - 1) / cell_h) * *gx;
-    return MA_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -403,118 +269,96 @@ int ma_qc_nmi_grid(ma_ctx* ctx, const uint8_t* ref, const uint8_t* b0, const uin
                    double* nmi0_host, double* nmi1_host, double* ncc0_host, double* ncc1_host)
 {
     MA_REQUIRE(ctx && ref && b0 && nmi0_host && ncc0_host && (!b1 || (nmi1_host && ncc1_host)), "NULL argument");
+    MaCellGrid g;
     long long ncells;
-    int gx;
-    MA_TRY(qc_grid(h, w, cell_h, cell_w, &ncells, &gx));
-    const int ch = cell_h < h ? cell_h : h, cw = cell_w < w ? cell_w : w;
-    MA_REQUIRE((unsigned long long)ch * (unsigned long long)cw < (1ull << 32), "a cell must hold fewer than 2^32 pixels");
+    MA_TRY(ma_cell_grid(h, w, cell_h, cell_w, &g, &ncells));
+    MA_REQUIRE((unsigned long long)g.ch * (unsigned long long)g.cw < (1ull << 32), "a cell must hold fewer than 2^32 pixels");
     const unsigned nimg = b1 ? 2 : 1;
-    // slice geometry of a full cell: balanced column segments of <= QC_SLICE columns, runs of rows that keep a slice <= QC_SLICE
-    const int n_seg = (cw + QC_SLICE - 1) / QC_SLICE;
-    const int seg_w = (cw + n_seg - 1) / n_seg;
-    const int rows_per = QC_SLICE / seg_w;
-    const long long slices = (long long)n_seg * ((ch + rows_per - 1) / rows_per);
+    // slice geometry of a full cell: balanced column segments of <= HIST_SLICE16 columns, runs of rows that keep a slice
+    // <= HIST_SLICE16
+    const int n_seg = (g.cw + HIST_SLICE16 - 1) / HIST_SLICE16;
+    const int seg_w = (g.cw + n_seg - 1) / n_seg;
+    const int rows_per = HIST_SLICE16 / seg_w;
+    const long long slices = (long long)n_seg * ((g.ch + rows_per - 1) / rows_per);
     MA_REQUIRE(slices <= 0x7fffffff, "cell too large");
     // per cell and label image: histogram (256 KiB), wave partials, moments, two scores
-    const size_t per = 65536 * sizeof(unsigned) + QC_PART * sizeof(double) + QC_RQ * QC_MOM * sizeof(unsigned long long) +
+    const size_t per = 65536 * sizeof(unsigned) + NR_PART * sizeof(double) + NR_Q * NR_MOM * sizeof(unsigned long long) +
                        2 * sizeof(double);
-    // at most QC_BATCH cells at a time: the histograms of a batch take 256 KiB per cell and image of the grow-only workspace
-    long long batch = (long long)(ctx->ws_limit / (per * nimg));
-    if (batch > ncells) batch = ncells;
-    if (batch > QC_BATCH) batch = QC_BATCH;
-    if (batch < 1) {
-        ma_set_error("workspace limit %zu is below the %zu bytes one cell takes", ctx->ws_limit, per * nimg);
-        return MA_ENOMEM;
-    }
-    MA_HIP(hipSetDevice(ctx->device));
-    MA_TRY(ma_ws_reserve(ctx, (size_t)batch * nimg * per));
-    MA_TRY(ma_pinned_reserve(ctx, (size_t)batch * nimg * 2 * sizeof(double)));
     const int vec_ok = ((((size_t)ref | (size_t)b0 | (size_t)(b1 ? b1 : b0)) & 15) == 0) ? 1 : 0;
-    for (long long c0 = 0; c0 < ncells; c0 += batch) {
-        const unsigned nb = (unsigned)(ncells - c0 < batch ? ncells - c0 : batch);
-        const unsigned nhist = nb * nimg;
-        unsigned* hist = (unsigned*)ctx->ws;
-        double* part = (double*)(hist + (size_t)nhist * 65536);
-        unsigned long long* mom = (unsigned long long*)(part + (size_t)nhist * QC_PART);
-        double* scores = (double*)(mom + (size_t)nhist * QC_RQ * QC_MOM);
-        const QcCells g{h, w, ch, cw, gx, c0};
-        {
+    // at most QC_BATCH cells at a time: the histograms of a batch take 256 KiB per cell and image of the grow-only workspace
+    return ma_cell_batches(
+        ctx, ncells, per * nimg, nimg * 2 * sizeof(double), QC_BATCH,
+        [&](long long c0, unsigned nb, const void** dev, size_t* bytes) -> int {
+            const unsigned nhist = nb * nimg;
+            unsigned* hist = (unsigned*)ctx->ws;
+            double* part = (double*)(hist + (size_t)nhist * 65536);
+            unsigned long long* mom = (unsigned long long*)(part + (size_t)nhist * NR_PART);
+            double* scores = (double*)(mom + (size_t)nhist * NR_Q * NR_MOM);
+            g.cell0 = c0;
             MaProfScope ps(ctx, MA_K_OTHER, (double)h * w * nimg * ((double)nb / ncells));
             MA_HIP(hipMemsetAsync(hist, 0, (size_t)nhist * 65536 * sizeof(unsigned), ctx->stream));
             hipLaunchKernelGGL((qc_joint_hist_kernel<1024>), dim3((unsigned)slices, nb, nimg), dim3(1024), 32768 * sizeof(unsigned),
                                ctx->stream, ref, b0, b1, g, seg_w, n_seg, rows_per, vec_ok, hist);
-            hipLaunchKernelGGL(qc_score_reduce_kernel, dim3(nhist, QC_RQ), dim3(QC_RT), 0, ctx->stream, (const unsigned*)hist, g, nb,
+            hipLaunchKernelGGL(qc_score_reduce_kernel, dim3(nhist, NR_Q), dim3(NR_T), 0, ctx->stream, (const unsigned*)hist, g, nb,
                                part, mom);
             hipLaunchKernelGGL(qc_score_final_kernel, dim3((nhist + 63) / 64), dim3(64), 0, ctx->stream, (const double*)part,
                                (const unsigned long long*)mom, g, nb, nhist, scores);
             MA_HIP(hipGetLastError());
-        }
-        double* pin = (double*)ctx->pinned;
-        MA_HIP(hipMemcpyAsync(pin, scores, (size_t)2 * nhist * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        MA_HIP(hipStreamSynchronize(ctx->stream));
-        for (unsigned i = 0; i < nb; i++) {
-            nmi0_host[c0 + i] = pin[i];
-            ncc0_host[c0 + i] = pin[nhist + i];
-            if (b1) {
-                nmi1_host[c0 + i] = pin[nb + i];
-                ncc1_host[c0 + i] = pin[nhist + nb + i];
+            *dev = scores;
+            *bytes = (size_t)2 * nhist * sizeof(double);
+            return MA_OK;
+        },
+        [&](long long c0, unsigned nb, const void* pinned) {
+            const double* pin = (const double*)pinned;
+            const unsigned nhist = nb * nimg;
+            for (unsigned i = 0; i < nb; i++) {
+                nmi0_host[c0 + i] = pin[i];
+                ncc0_host[c0 + i] = pin[nhist + i];
+                if (b1) {
+                    nmi1_host[c0 + i] = pin[nb + i];
+                    ncc1_host[c0 + i] = pin[nhist + nb + i];
+                }
             }
-        }
-    }
-    if (ctx->profile) MA_TRY(ma_profile_flush(ctx));
-    return MA_OK;
+        });
 }
 
 int ma_qc_flow_grid(ma_ctx* ctx, const float* flow, int h, int w, int cell_h, int cell_w, double* jac_min_host,
                     long long* folded_host, long long* invalid_host, double* flow_mean_host, double* flow_max_host)
 {
     MA_REQUIRE(ctx && flow && jac_min_host && folded_host && invalid_host && flow_mean_host && flow_max_host, "NULL argument");
+    MaCellGrid g;
     long long ncells;
-    int gx;
-    MA_TRY(qc_grid(h, w, cell_h, cell_w, &ncells, &gx));
+    MA_TRY(ma_cell_grid(h, w, cell_h, cell_w, &g, &ncells));
     MA_REQUIRE(((size_t)flow & 7) == 0, "flow must be 8-byte aligned");
-    const int ch = cell_h < h ? cell_h : h, cw = cell_w < w ? cell_w : w;
-    const int ntx = (cw + QF_TW - 1) / QF_TW;
-    const long long ntiles = (long long)ntx * ((ch + QF_TH - 1) / QF_TH);
+    const int ntx = (g.cw + QF_TW - 1) / QF_TW;
+    const long long ntiles = (long long)ntx * ((g.ch + QF_TH - 1) / QF_TH);
     MA_REQUIRE(ntiles <= 0x7fffffff, "cell too large");
-    const size_t per = (size_t)ntiles * sizeof(QcFlowPart) + 5 * sizeof(double);
-    long long batch = (long long)(ctx->ws_limit / per);
-    if (batch > ncells) batch = ncells;
-    if (batch > 65535) batch = 65535;
-    if (batch < 1) {
-        ma_set_error("workspace limit %zu is below the %zu bytes one cell takes", ctx->ws_limit, per);
-        return MA_ENOMEM;
-    }
-    MA_HIP(hipSetDevice(ctx->device));
-    MA_TRY(ma_ws_reserve(ctx, (size_t)batch * per));
-    MA_TRY(ma_pinned_reserve(ctx, (size_t)batch * 5 * sizeof(double)));
     const int vec_ok = ((size_t)flow & 15) == 0 ? 1 : 0;
-    for (long long c0 = 0; c0 < ncells; c0 += batch) {
-        const unsigned nb = (unsigned)(ncells - c0 < batch ? ncells - c0 : batch);
-        QcFlowPart* part = (QcFlowPart*)ctx->ws;
-        double* res = (double*)(part + (size_t)nb * ntiles);
-        const QcCells g{h, w, ch, cw, gx, c0};
-        {
+    return ma_cell_batches(
+        ctx, ncells, (size_t)ntiles * sizeof(QcFlowPart) + 5 * sizeof(double), 5 * sizeof(double), 65535,
+        [&](long long c0, unsigned nb, const void** dev, size_t* bytes) -> int {
+            QcFlowPart* part = (QcFlowPart*)ctx->ws;
+            double* res = (double*)(part + (size_t)nb * ntiles);
+            g.cell0 = c0;
             MaProfScope ps(ctx, MA_K_OTHER, (double)h * w * ((double)nb / ncells));
             hipLaunchKernelGGL(qc_flow_tile_kernel, dim3((unsigned)ntiles, nb), dim3(QF_T), 0, ctx->stream, flow, g, ntx,
                                (int)ntiles, vec_ok, part);
             hipLaunchKernelGGL(qc_flow_cell_kernel, dim3(nb), dim3(QF_RT), 0, ctx->stream, (const QcFlowPart*)part, (int)ntiles, res);
             MA_HIP(hipGetLastError());
-        }
-        double* pin = (double*)ctx->pinned;
-        MA_HIP(hipMemcpyAsync(pin, res, (size_t)nb * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        MA_HIP(hipStreamSynchronize(ctx->stream));
-        for (unsigned i = 0; i < nb; i++) {
-            const double* r = pin + (size_t)i * 5;
-            jac_min_host[c0 + i] = r[0];
-            folded_host[c0 + i] = (long long)r[1];
-            invalid_host[c0 + i] = (long long)r[2];
-            flow_mean_host[c0 + i] = r[3];
-            flow_max_host[c0 + i] = r[4];
-        }
-    }
-    if (ctx->profile) MA_TRY(ma_profile_flush(ctx));
-    return MA_OK;
+            *dev = res;
+            *bytes = (size_t)nb * 5 * sizeof(double);
+            return MA_OK;
+        },
+        [&](long long c0, unsigned nb, const void* pinned) {
+            for (unsigned i = 0; i < nb; i++) {
+                const double* r = (const double*)pinned + (size_t)i * 5;
+                jac_min_host[c0 + i] = r[0];
+                folded_host[c0 + i] = (long long)r[1];
+                invalid_host[c0 + i] = (long long)r[2];
+                flow_mean_host[c0 + i] = r[3];
+                flow_max_host[c0 + i] = r[4];
+            }
+        });
 }
 
 } // extern "C"

@@ -5,7 +5,7 @@
 // Every moment is an integer and is summed exactly (u32 inside a tile, u64 beyond), so the table of scores does not depend
 // on the tiling, the batching or the order of the atomics; the scores themselves are formed once, in f64, by the finishing
 // kernel.
-#include "ma_internal.h"
+#include "cell_grid.h"
 #include "../../include/microaligner_residual.h"
 
 #include <cmath>
@@ -14,20 +14,14 @@
 namespace {
 
 // ---- geometry -----------------------------------------------------------------------------------------------------
-struct RsGrid {
-    int h, w, ch, cw, gx, R;
-    long long cell0;   // first cell of the batch (row-major cell index)
-};
-
 // comparison domain of a cell: the cell cut back to [R, h - R) x [R, w - R); empty when oy1 <= oy0 or ox1 <= ox0
-__device__ __forceinline__ void rs_domain(const RsGrid& g, long long cell, int& oy0, int& oy1, int& ox0, int& ox1)
+__device__ __forceinline__ void rs_domain(const MaCellGrid& g, int R, long long cell, int& oy0, int& oy1, int& ox0, int& ox1)
 {
-    const int ci = (int)(cell / g.gx), cj = (int)(cell % g.gx);
-    const int y0 = ci * g.ch, x0 = cj * g.cw;
-    oy0 = max(y0, g.R);
-    oy1 = min(min(y0 + g.ch, g.h), g.h - g.R);
-    ox0 = max(x0, g.R);
-    ox1 = min(min(x0 + g.cw, g.w), g.w - g.R);
+    g.rect(cell, oy0, oy1, ox0, ox1);
+    oy0 = max(oy0, R);
+    oy1 = min(oy1, g.h - R);
+    ox0 = max(ox0, R);
+    ox1 = min(ox1, g.w - R);
 }
 
 // ---- correlation kernel -----------------------------------------------------------------------------------------------
@@ -90,7 +84,7 @@ __device__ __forceinline__ unsigned rs_load4(const uint8_t* __restrict__ img, in
 }
 
 __global__ __launch_bounds__(RS_NT) void rs_corr_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b0,
-                                                        const uint8_t* __restrict__ b1, RsGrid g, RsLds L, int nchunk, int tpb,
+                                                        const uint8_t* __restrict__ b1, MaCellGrid g, RsLds L, int nchunk, int tpb,
                                                         int G, int KS, unsigned long long* __restrict__ mom)
 {
     extern __shared__ unsigned long long rs_smem[];
@@ -104,7 +98,7 @@ __global__ __launch_bounds__(RS_NT) void rs_corr_kernel(const uint8_t* __restric
     const uint8_t* __restrict__ b = blockIdx.z ? b1 : b0;
     const int R = L.R, D = L.D, NS = L.NS, BPd = L.BPd, NQ = (D + 3) >> 2;
     int oy0, oy1, ox0, ox1;
-    rs_domain(g, g.cell0 + blockIdx.y, oy0, oy1, ox0, ox1);
+    rs_domain(g, R, g.cell0 + blockIdx.y, oy0, oy1, ox0, ox1);
     const int strip = blockIdx.x / nchunk, chunk = blockIdx.x % nchunk;
     const int tx0 = ox0 + strip * RS_TW;
     const int cy0 = oy0 + chunk * tpb * RS_TH;
@@ -204,17 +198,15 @@ __global__ __launch_bounds__(RS_NT) void rs_corr_kernel(const uint8_t* __restric
 // ---- finishing kernel ---------------------------------------------------------------------------------------------
 // One block per (label image, cell): the scores of all shifts in f64, then the peak, the refinement and the flags by one
 // thread (a scan of at most 33 * 33 scores in the order of the tie rule).
-__device__ __forceinline__ bool rs_finite(double x) { return x - x == 0.0; }
-
-__global__ __launch_bounds__(RS_NT) void rs_finish_kernel(const unsigned long long* __restrict__ mom, RsGrid g, unsigned ncells,
-                                                          double* __restrict__ res, uint8_t* __restrict__ flags,
+__global__ __launch_bounds__(RS_NT) void rs_finish_kernel(const unsigned long long* __restrict__ mom, MaCellGrid g, int R,
+                                                          unsigned ncells, double* __restrict__ res, uint8_t* __restrict__ flags,
                                                           double* __restrict__ table)
 {
     __shared__ double sc[(2 * MA_RESIDUAL_MAX_SHIFT + 1) * (2 * MA_RESIDUAL_MAX_SHIFT + 1)];
-    const int R = g.R, D = 2 * R + 1, NS = D * D;
+    const int D = 2 * R + 1, NS = D * D;
     const unsigned long long* m = mom + (size_t)blockIdx.x * (size_t)(3 * NS + 2);
     int oy0, oy1, ox0, ox1;
-    rs_domain(g, g.cell0 + blockIdx.x % ncells, oy0, oy1, ox0, ox1);
+    rs_domain(g, R, g.cell0 + blockIdx.x % ncells, oy0, oy1, ox0, ox1);
     const long long n = (oy1 > oy0 && ox1 > ox0) ? (long long)(oy1 - oy0) * (long long)(ox1 - ox0) : 0;
     const long long S_a = (long long)m[3 * NS], S_aa = (long long)m[3 * NS + 1];
     const long long va = n * S_aa - S_a * S_a;
@@ -230,7 +222,7 @@ __global__ __launch_bounds__(RS_NT) void rs_finish_kernel(const unsigned long lo
     int best = -1, bestd2 = 0;
     for (int s = 0; s < NS; s++) {          // dy ascending, then dx ascending: among equal scores and distances the first stays
         const double v = sc[s];
-        if (!rs_finite(v)) continue;
+        if (!ma_finite(v)) continue;
         const int dy = s / D - R, dx = s % D - R, d2 = dx * dx + dy * dy;
         if (best < 0 || v > sc[best] || (v == sc[best] && d2 < bestd2)) { best = s; bestd2 = d2; }
     }
@@ -247,7 +239,7 @@ __global__ __launch_bounds__(RS_NT) void rs_finish_kernel(const unsigned long lo
     auto refine = [&](int pos, int stride) {
         if (pos == 0 || pos == D - 1) return 0.0;
         const double sm = sc[best - stride], sp = sc[best + stride];
-        if (!rs_finite(sm) || !rs_finite(sp)) return 0.0;
+        if (!ma_finite(sm) || !ma_finite(sp)) return 0.0;
         const double den = sm - 2.0 * s0 + sp;
         if (!(den < 0.0)) return 0.0;
         const double d = 0.5 * (sm - sp) / den;
@@ -274,12 +266,11 @@ int ma_residual_shift_grid(ma_ctx* ctx, const uint8_t* ref, const uint8_t* b0, c
     MA_REQUIRE(ctx && ref && b0 && shift_x0 && shift_y0 && score0_peak && score0_zero && at_limit0 && valid0, "NULL argument");
     MA_REQUIRE(!b1 || (shift_x1 && shift_y1 && score1_peak && score1_zero && at_limit1 && valid1), "NULL argument");
     MA_REQUIRE(max_shift >= 1 && max_shift <= MA_RESIDUAL_MAX_SHIFT, "max_shift must be in 1 .. 16");
-    MA_REQUIRE(h > 0 && w > 0, "empty image");
-    MA_REQUIRE(cell_h > 0 && cell_w > 0, "cell size must be >= 1");
-    const int ch = cell_h < h ? cell_h : h, cw = cell_w < w ? cell_w : w;
-    MA_REQUIRE((long long)ch * cw <= MA_RESIDUAL_MAX_CELL_PIXELS, "a cell must hold at most 2^23 pixels");
-    const int R = max_shift, gx = (w + cell_w - 1) / cell_w;
-    const long long ncells = (long long)((h + cell_h - 1) / cell_h) * gx;
+    MaCellGrid g;
+    long long ncells;
+    MA_TRY(ma_cell_grid(h, w, cell_h, cell_w, &g, &ncells));
+    MA_REQUIRE((long long)g.ch * g.cw <= MA_RESIDUAL_MAX_CELL_PIXELS, "a cell must hold at most 2^23 pixels");
+    const int R = max_shift;
     const unsigned nimg = b1 ? 2 : 1;
     const bool want_table = table0 || (b1 && table1);
     const RsLds L = rs_lds_layout(R);
@@ -288,7 +279,7 @@ int ma_residual_shift_grid(ma_ctx* ctx, const uint8_t* ref, const uint8_t* b0, c
     // blocks of a full cell: strips of RS_TW columns, each cut into chunks of tpb tiles of RS_TH rows.  tpb trades global
     // atomics (one flush of the block's accumulators per chunk) against blocks in flight: aim at >= 4096 blocks, at most
     // 16 tiles a block.
-    const int nstrip = (cw + RS_TW - 1) / RS_TW, ntile = (ch + RS_TH - 1) / RS_TH;
+    const int nstrip = (g.cw + RS_TW - 1) / RS_TW, ntile = (g.ch + RS_TH - 1) / RS_TH;
     int tpb = 16;
     while (tpb > 1 && (double)ncells * nimg * nstrip * ((ntile + tpb - 1) / tpb) < 4096.0) tpb >>= 1;
     const int nchunk = (ntile + tpb - 1) / tpb;
@@ -302,65 +293,57 @@ int ma_residual_shift_grid(ma_ctx* ctx, const uint8_t* ref, const uint8_t* b0, c
     // per cell and label image: the u64 moments; four doubles, two flags and, if asked for, the table of scores
     const size_t mom_per = (size_t)(3 * NS + 2) * sizeof(unsigned long long);
     const size_t out_per = 4 * sizeof(double) + (want_table ? (size_t)NS * sizeof(double) : 0) + 2;
-    const size_t per = (mom_per + out_per) * nimg;
-    long long batch = (long long)(ctx->ws_limit / per);
-    if (batch > ncells) batch = ncells;
-    if (batch > MA_GRID_Y_MAX) batch = MA_GRID_Y_MAX;
-    const long long pin_cap = (long long)(((size_t)64 << 20) / (out_per * nimg));   // page-locked staging stays <= 64 MiB
-    if (batch > pin_cap) batch = pin_cap;
-    if (batch < 1) {
-        ma_set_error("workspace limit %zu is below the %zu bytes one cell takes", ctx->ws_limit, per);
-        return MA_ENOMEM;
-    }
-    MA_HIP(hipSetDevice(ctx->device));
-    MA_TRY(ma_ws_reserve(ctx, (size_t)batch * per));
-    MA_TRY(ma_pinned_reserve(ctx, (size_t)batch * nimg * out_per));
-    for (long long c0 = 0; c0 < ncells; c0 += batch) {
-        const unsigned nb = (unsigned)(ncells - c0 < batch ? ncells - c0 : batch);
-        const size_t nblk = (size_t)nb * nimg;
-        unsigned long long* mom = (unsigned long long*)ctx->ws;
-        double* res = (double*)(mom + nblk * (size_t)(3 * NS + 2));
-        double* tab = res + nblk * 4;
-        uint8_t* flags = (uint8_t*)(tab + (want_table ? nblk * (size_t)NS : 0));
-        const size_t out_bytes = (size_t)((uint8_t*)(flags + nblk * 2) - (uint8_t*)res);
-        const RsGrid g{h, w, ch, cw, gx, R, c0};
-        MA_HIP(hipMemsetAsync(mom, 0, nblk * mom_per, ctx->stream));
-        {
-            MaProfScope ps(ctx, MA_K_OTHER, (double)h * w * nimg * ((double)nb / ncells));
-            hipLaunchKernelGGL(rs_corr_kernel, dim3((unsigned)(nstrip * nchunk), nb, nimg), dim3(RS_NT), L.bytes, ctx->stream, ref, b0,
-                               b1, g, L, nchunk, tpb, G, KS, mom);
-        }
-        hipLaunchKernelGGL(rs_finish_kernel, dim3((unsigned)nblk), dim3(RS_NT), 0, ctx->stream, (const unsigned long long*)mom, g, nb,
-                           res, flags, want_table ? tab : (double*)nullptr);
-        MA_HIP(hipGetLastError());
-        uint8_t* pin = (uint8_t*)ctx->pinned;
-        MA_HIP(hipMemcpyAsync(pin, res, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        MA_HIP(hipStreamSynchronize(ctx->stream));
-        const double* pres = (const double*)pin;
-        const double* ptab = pres + nblk * 4;
-        const uint8_t* pfl = (const uint8_t*)(ptab + (want_table ? nblk * (size_t)NS : 0));
-        for (unsigned im = 0; im < nimg; im++) {
-            double* sx = im ? shift_x1 : shift_x0;
-            double* sy = im ? shift_y1 : shift_y0;
-            double* sp = im ? score1_peak : score0_peak;
-            double* sz = im ? score1_zero : score0_zero;
-            uint8_t* al = im ? at_limit1 : at_limit0;
-            uint8_t* va = im ? valid1 : valid0;
-            double* tb = im ? table1 : table0;
-            for (unsigned i = 0; i < nb; i++) {
-                const size_t k = (size_t)im * nb + i;
-                sx[c0 + i] = pres[4 * k];
-                sy[c0 + i] = pres[4 * k + 1];
-                sp[c0 + i] = pres[4 * k + 2];
-                sz[c0 + i] = pres[4 * k + 3];
-                al[c0 + i] = pfl[2 * k];
-                va[c0 + i] = pfl[2 * k + 1];
-                if (tb) memcpy(tb + (size_t)(c0 + i) * NS, ptab + k * NS, (size_t)NS * sizeof(double));
+    long long cap = (long long)(((size_t)64 << 20) / (out_per * nimg));   // page-locked staging stays <= 64 MiB
+    if (cap > MA_GRID_Y_MAX) cap = MA_GRID_Y_MAX;
+    // results of a batch, on the device and in the page-locked copy: [nblk][4] doubles, the tables, [nblk][2] flags
+    const size_t tab_per = want_table ? (size_t)NS : 0;
+    return ma_cell_batches(
+        ctx, ncells, (mom_per + out_per) * nimg, out_per * nimg, cap,
+        [&](long long c0, unsigned nb, const void** dev, size_t* bytes) -> int {
+            const size_t nblk = (size_t)nb * nimg;
+            unsigned long long* mom = (unsigned long long*)ctx->ws;
+            double* res = (double*)(mom + nblk * (size_t)(3 * NS + 2));
+            double* tab = res + nblk * 4;
+            uint8_t* flags = (uint8_t*)(tab + nblk * tab_per);
+            g.cell0 = c0;
+            MA_HIP(hipMemsetAsync(mom, 0, nblk * mom_per, ctx->stream));
+            {
+                MaProfScope ps(ctx, MA_K_OTHER, (double)h * w * nimg * ((double)nb / ncells));
+                hipLaunchKernelGGL(rs_corr_kernel, dim3((unsigned)(nstrip * nchunk), nb, nimg), dim3(RS_NT), L.bytes, ctx->stream, ref,
+                                   b0, b1, g, L, nchunk, tpb, G, KS, mom);
             }
-        }
-    }
-    if (ctx->profile) MA_TRY(ma_profile_flush(ctx));
-    return MA_OK;
+            hipLaunchKernelGGL(rs_finish_kernel, dim3((unsigned)nblk), dim3(RS_NT), 0, ctx->stream, (const unsigned long long*)mom, g,
+                               R, nb, res, flags, want_table ? tab : (double*)nullptr);
+            MA_HIP(hipGetLastError());
+            *dev = res;
+            *bytes = nblk * out_per;
+            return MA_OK;
+        },
+        [&](long long c0, unsigned nb, const void* pinned) {
+            const size_t nblk = (size_t)nb * nimg;
+            const double* pres = (const double*)pinned;
+            const double* ptab = pres + nblk * 4;
+            const uint8_t* pfl = (const uint8_t*)(ptab + nblk * tab_per);
+            for (unsigned im = 0; im < nimg; im++) {
+                double* sx = im ? shift_x1 : shift_x0;
+                double* sy = im ? shift_y1 : shift_y0;
+                double* sp = im ? score1_peak : score0_peak;
+                double* sz = im ? score1_zero : score0_zero;
+                uint8_t* al = im ? at_limit1 : at_limit0;
+                uint8_t* va = im ? valid1 : valid0;
+                double* tb = im ? table1 : table0;
+                for (unsigned i = 0; i < nb; i++) {
+                    const size_t k = (size_t)im * nb + i;
+                    sx[c0 + i] = pres[4 * k];
+                    sy[c0 + i] = pres[4 * k + 1];
+                    sp[c0 + i] = pres[4 * k + 2];
+                    sz[c0 + i] = pres[4 * k + 3];
+                    al[c0 + i] = pfl[2 * k];
+                    va[c0 + i] = pfl[2 * k + 1];
+                    if (tb) memcpy(tb + (size_t)(c0 + i) * NS, ptab + k * NS, (size_t)NS * sizeof(double));
+                }
+            }
+        });
 }
 
 } // extern "C"

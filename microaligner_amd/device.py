@@ -983,15 +983,24 @@ class Context:
         return (np.frombuffer(s0, dtype=np.float64, count=got.value).copy(),
                 np.frombuffer(s1, dtype=np.float64, count=got.value).copy())
 
+    # per-cell maps: the checks and the grid shape the three calls below share -----------------------------------------
+    @staticmethod
+    def _check_cell_labels(ref, b0, b1, what):
+        for b in (b0, b1):
+            if b is not None and (ref.dtype != np.uint8 or b.dtype != np.uint8 or ref.shape != b.shape or ref.ndim != 2):
+                raise ValueError(f"{what} labels must be 2-D uint8 arrays of equal shape")
+
+    @staticmethod
+    def _cell_grid_shape(h, w, cell_h, cell_w):
+        return -(-h // int(cell_h)), -(-w // int(cell_w))
+
     # registration quality maps (include/microaligner_qc.h) ------------------------------------------------------------
     def qc_nmi_grid(self, ref, b0, b1, cell_h, cell_w):
         """Per cell of the (cell_h, cell_w) grid: NMI and Pearson r of the u8 labels (ref, b0) and, unless b1 is None,
         (ref, b1).  -> (nmi0, nmi1, ncc0, ncc1), each (gy, gx) float64 (the b1 pair None without b1)."""
-        for b in (b0, b1):
-            if b is not None and (ref.dtype != np.uint8 or b.dtype != np.uint8 or ref.shape != b.shape or ref.ndim != 2):
-                raise ValueError("QC labels must be 2-D uint8 arrays of equal shape")
+        self._check_cell_labels(ref, b0, b1, "QC")
         h, w = ref.shape
-        gy, gx = -(-h // int(cell_h)), -(-w // int(cell_w))
+        gy, gx = self._cell_grid_shape(h, w, cell_h, cell_w)
         pd = C.POINTER(C.c_double)
         nmi0, ncc0 = np.empty((gy, gx)), np.empty((gy, gx))
         nmi1, ncc1 = (np.empty((gy, gx)), np.empty((gy, gx))) if b1 is not None else (None, None)
@@ -1005,7 +1014,7 @@ class Context:
         if flow.dtype != np.float32 or flow.ndim != 3 or flow.shape[2] != 2:
             raise ValueError(f"flow must be float32 of shape (H, W, 2), got {flow.dtype} {flow.shape}")
         h, w = flow.shape[:2]
-        gy, gx = -(-h // int(cell_h)), -(-w // int(cell_w))
+        gy, gx = self._cell_grid_shape(h, w, cell_h, cell_w)
         pd, pl = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
         jmin, mean, mx = np.empty((gy, gx)), np.empty((gy, gx)), np.empty((gy, gx))
         folded, invalid = np.empty((gy, gx), np.int64), np.empty((gy, gx), np.int64)
@@ -1019,12 +1028,10 @@ class Context:
         b1 is None, (ref, b1).  -> (maps0, maps1), each a dict of (gy, gx) arrays shift_x, shift_y, score, score0 (float64),
         at_limit, valid (bool) and table ((gy, gx, 2R + 1, 2R + 1) float64, or None without table=True); maps1 is None
         without b1."""
-        for b in (b0, b1):
-            if b is not None and (ref.dtype != np.uint8 or b.dtype != np.uint8 or ref.shape != b.shape or ref.ndim != 2):
-                raise ValueError("residual shift labels must be 2-D uint8 arrays of equal shape")
+        self._check_cell_labels(ref, b0, b1, "residual shift")
         h, w = ref.shape
         R = int(max_shift)
-        gy, gx = -(-h // int(cell_h)), -(-w // int(cell_w))
+        gy, gx = self._cell_grid_shape(h, w, cell_h, cell_w)
         pd, pb = C.POINTER(C.c_double), C.POINTER(C.c_ubyte)
 
         def outputs(wanted):

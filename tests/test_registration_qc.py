@@ -95,7 +95,8 @@ def test_qc_header_library_and_bindings_agree():
 
 def test_quality_maps_stay_out_of_the_measured_path_hash(tmp_path, monkeypatch):
     """build.source_hash() names the kernels a profile measured (bench.py quotes PMC traffic only for a matching hash):
-    editing qc.hip or its header must leave it unchanged, editing a measured-path source must change it."""
+    editing qc.hip, its header or the cell grid must leave it unchanged, editing a measured-path source or the gate's
+    score, which qc.hip shares with nmi.hip, must change it."""
     import shutil
     from microaligner_amd import build
     assert "qc.hip" in build.SOURCES and QC_HEADER not in [os.path.abspath(h) for h in build.HEADERS]
@@ -115,9 +116,16 @@ def test_quality_maps_stay_out_of_the_measured_path_hash(tmp_path, monkeypatch):
     with open(csrc / "qc.hip", "a") as f:
         f.write("\n// edited\n")
     assert build.source_hash() == out
+    with open(csrc / "cell_grid.h", "a") as f:
+        f.write("\n// edited\n")
+    assert build.source_hash() == out
+    with open(csrc / "nmi_score.h", "a") as f:
+        f.write("\n// edited\n")
+    scored = build.source_hash()
+    assert scored != out
     with open(csrc / "dog.hip", "a") as f:
         f.write("\n// edited\n")
-    assert build.source_hash() != out
+    assert build.source_hash() not in (out, scored)
 
 
 # ---- numpy statements ------------------------------------------------------------------------------------------------
@@ -407,6 +415,36 @@ def test_results_do_not_depend_on_inputs_batching_or_repetition(ctx):
         for k in ("flow_mean", "flow_max", "jac_min", "folded", "invalid"):
             assert np.array_equal(getattr(tiny_cells, k), getattr(big, k), equal_nan=True)
     assert_flow_stats(big, flow, (3, 2))
+
+
+@pytest.mark.gpu
+def test_nmi_grid_one_image_batches(ctx):
+    """ma_qc_nmi_grid without b1 (assess_registration always passes two images): the batch's results lie at pin[i] and
+    pin[nb + i].  Under a 1 MiB workspace limit a cell and image take 262 576 B, so the one-image call runs in batches of
+    3 cells and the two-image call in batches of 1."""
+    from microaligner_amd import _lib as L
+    rng = np.random.default_rng(20)
+    H, W, cell = 100, 90, (32, 40)
+    ref, l0, l1 = labels_u8(rng, (H, W)), labels_u8(rng, (H, W)), labels_u8(rng, (H, W))
+    d_ref, b0, b1 = (ctx.asdevice(x) for x in (ref, l0, l1))
+    full = ctx.qc_nmi_grid(d_ref, b0, None, *cell)
+    prev = ctx.get_option(L.MA_OPT_WORKSPACE_LIMIT)
+    try:
+        ctx.set_option(L.MA_OPT_WORKSPACE_LIMIT, 1 << 20)
+        one = ctx.qc_nmi_grid(d_ref, b0, None, *cell)
+        two = ctx.qc_nmi_grid(d_ref, b0, b1, *cell)
+    finally:
+        ctx.set_option(L.MA_OPT_WORKSPACE_LIMIT, prev)
+    nmi0, nmi1, ncc0, ncc1 = one
+    assert nmi1 is None and ncc1 is None and full[1] is None and full[3] is None
+    assert nmi0.shape == (4, 3) and ncc0.shape == (4, 3)
+    for got in (two, full):
+        assert np.array_equal(nmi0, got[0]) and np.array_equal(ncc0, got[2])
+    assert np.isfinite(ncc0).all()
+    for i in range(4):
+        for j in range(3):
+            y0, x0 = 32 * i, 40 * j
+            assert nmi0[i, j] == crop_nmi(ctx, ref[y0:y0 + 32, x0:x0 + 40], l0[y0:y0 + 32, x0:x0 + 40]), (i, j)
 
 
 @pytest.mark.gpu

@@ -352,7 +352,10 @@ def test_residual_shift_stays_out_of_the_measured_path_hash(tmp_path, monkeypatc
     as it is, an edit of dog.hip changes it; and the hash is what the commit without the feature computes."""
     from microaligner_amd import build
     assert "residual_shift.hip" in build.SOURCES and HEADER not in [os.path.abspath(h) for h in build.HEADERS]
-    assert [os.path.abspath(h) for h in build.SOURCE_HEADERS["residual_shift.hip"]] == [HEADER]
+    # its own headers: the public one and the cell grid it shares with qc.hip, neither among the hashed ones
+    own = [os.path.abspath(h) for h in build.SOURCE_HEADERS["residual_shift.hip"]]
+    assert own == [HEADER, os.path.join(build.CSRC, "cell_grid.h")]
+    assert not set(own) & {os.path.abspath(h) for h in build.HEADERS}
     out = subprocess.run([sys.executable, "-c", "from microaligner_amd import build; print(build.source_hash())"], cwd=ROOT,
                          capture_output=True, text=True, check=True).stdout.strip()
     assert out == build.source_hash() and re.fullmatch(r"[0-9a-f]{16}", out)
