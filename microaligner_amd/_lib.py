@@ -183,6 +183,19 @@ RESIDUAL_SIGNATURES = {
     "ma_residual_shift_grid": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i] + _residual_outputs + _residual_outputs),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_flowgrid.h (grid flows)
+FLOWGRID_SIGNATURES = {
+    "ma_flow_grid_sample": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ma_flow_grid_expand": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ma_flow_grid_error": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, C.POINTER(_f), C.POINTER(C.c_longlong),
+                                C.POINTER(C.c_longlong)]),
+    "ma_warp_affine_grid": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, C.POINTER(_d), _vp, _i]),
+    "ma_warp_affine_grid_pages_host": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i,
+                                            C.POINTER(_d), _i]),
+    "ma_transform_points_grid": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(_d), C.POINTER(_d), _i, _i, _i, _i, _d, _vp, _vp,
+                                      _vp]),
+}
+
 _lib = None
 
 
@@ -198,7 +211,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + \
             list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()) + list(FLOWINVERT_SIGNATURES.items()) + \
-            list(RESIDUAL_SIGNATURES.items()):
+            list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

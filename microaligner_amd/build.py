@@ -15,18 +15,23 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
-           "flow_compose.hip", "flow_invert.hip", "residual_shift.hip"]
+           "flow_compose.hip", "flow_invert.hip", "residual_shift.hip", "flow_grid.hip"]
 HEADERS = [os.path.join(CSRC, "ma_internal.h"), os.path.join(CSRC, "remap_common.h"), os.path.join(CSRC, "nmi_score.h"),
            os.path.join(HERE, "..", "include", "microaligner_hip.h")]
 # headers of single sources that are off the measured path (not in HEADERS, so not in source_hash())
 _INTERP_HEADERS = [os.path.join(HERE, "..", "include", "microaligner_interp.h"), os.path.join(CSRC, "remap_interp.h")]
 _CELL_GRID = os.path.join(CSRC, "cell_grid.h")
+_FLOW_GRID = [os.path.join(HERE, "..", "include", "microaligner_flowgrid.h"), os.path.join(CSRC, "flow_grid_eval.h")]
 SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_qc.h"), _CELL_GRID],
                   "remap_interp.hip": _INTERP_HEADERS,
                   "warp_compose.hip": _INTERP_HEADERS + [os.path.join(HERE, "..", "include", "microaligner_compose.h")],
                   "flow_compose.hip": [os.path.join(HERE, "..", "include", "microaligner_flowcompose.h")],
                   "flow_invert.hip": [os.path.join(HERE, "..", "include", "microaligner_flowinvert.h")],
-                  "residual_shift.hip": [os.path.join(HERE, "..", "include", "microaligner_residual.h"), _CELL_GRID]}
+                  "residual_shift.hip": [os.path.join(HERE, "..", "include", "microaligner_residual.h"), _CELL_GRID],
+                  "flow_grid.hip": _FLOW_GRID + [_CELL_GRID]}
+# the grid-flow headers are also read by the two sources whose kernels take their flow from a grid: further dependencies of
+# those sources, beside the headers of their own above
+GRID_FLOW_USERS = {"warp_compose.hip": _FLOW_GRID, "flow_invert.hip": _FLOW_GRID}
 # -fno-slp-vectorize: the SLP vectoriser packs the sliding-window blur into v_pk_* ops with a storm of
 # register-pair shuffles (measured 1.65x slower on blur_h_solve, profiles/r01_*); packed math is written by hand
 # where it pays.
@@ -71,10 +76,12 @@ def source_hash():
     #   - the exact flow composition, which only flow_composition="exact" reaches;
     #   - the flow inverse and the point transforms, which only invert_flow() / transform_points() reach;
     #   - the residual shift maps, which only residual_shift() reaches;
+    #   - the grid flows (nodes, expansion, loss maps; flow_grid_eval.h, their evaluation inside the warp and the point
+    #     kernels), which only compress_flow() / a FlowGrid reach;
     #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps (SOURCE_HEADERS).
     off_path = {"probe.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "affine.hip", "qc.hip",
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
-                "flow_invert.hip", "residual_shift.hip"}
+                "flow_invert.hip", "residual_shift.hip", "flow_grid.hip"}
     for path in [os.path.join(CSRC, s) for s in SOURCES if s not in off_path] + HEADERS:
         h.update(open(path, "rb").read())
     h.update(" ".join(_flags()).encode())
@@ -97,7 +104,7 @@ def build(force=False, verbose=False):
         src = os.path.join(CSRC, s)
         obj = os.path.join(objdir, s.replace(".hip", ".o"))
         objs.append(obj)
-        deps = [src] + HEADERS + SOURCE_HEADERS.get(s, []) + ([hash_h] if s == "ma_api.hip" else [])
+        deps = [src] + HEADERS + SOURCE_HEADERS.get(s, []) + GRID_FLOW_USERS.get(s, []) + ([hash_h] if s == "ma_api.hip" else [])
         if force or _stale(obj, deps):
             jobs.append([hipcc] + _flags() + ["-I", objdir, "-c", src, "-o", obj])
 

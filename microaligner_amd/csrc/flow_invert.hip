@@ -7,6 +7,8 @@
 // gathered float2 taps per step; the taps of a step lie within |g| px of the pixel, so neighbouring lanes share their
 // cache lines.  Lanes finish at different steps: a wave runs until its last lane stops.
 #include "../../include/microaligner_flowinvert.h"
+#include "../../include/microaligner_flowgrid.h"
+#include "flow_grid_eval.h"
 #include "ma_internal.h"
 
 #include <cmath>
@@ -126,8 +128,17 @@ __device__ __forceinline__ double2 sample_f64(const float2* __restrict__ f, int 
     return make_double2(topx * by + botx * ay, topy * by + boty * ay);
 }
 
-// `pts` and `out` may be one array: neither is __restrict__, and a thread reads only the point it writes
-__global__ __launch_bounds__(256) void transform_points_kernel(const double2* pts, int n, const float2* __restrict__ f, int H,
+// the float64 sampler of the dense flow, S64 of the header; the one of a grid flow is flow_grid_eval.h's FgSampler64
+struct DenseSampler64 {
+    const float2* __restrict__ f;
+    int H, W;
+    __device__ __forceinline__ double2 operator()(double mx, double my) const { return sample_f64(f, H, W, mx, my); }
+};
+
+// `pts` and `out` may be one array: neither is __restrict__, and a thread reads only the point it writes.  S: the sampler
+// of the (H, W) flow.
+template <class S>
+__global__ __launch_bounds__(256) void transform_points_kernel(const double2* pts, int n, S sample, int H,
                                                                int W, Mat6 A, double padx, double pady, int direction,
                                                                int max_iter, double tol, double2* out,
                                                                unsigned char* __restrict__ converged,
@@ -144,7 +155,7 @@ __global__ __launch_bounds__(256) void transform_points_kernel(const double2* pt
     }
     const double wmax = (double)(W - 1), hmax = (double)(H - 1);
     if (direction == MA_POINTS_TO_MOVING) {
-        const double2 s = sample_f64(f, H, W, p.x, p.y);
+        const double2 s = sample(p.x, p.y);
         const double ux = p.x - s.x, uy = p.y - s.y;
         out[i] = make_double2(((A.v[0] * ux + A.v[1] * uy) + A.v[2]) - padx, ((A.v[3] * ux + A.v[4] * uy) + A.v[5]) - pady);
         converged[i] = 1;
@@ -156,7 +167,7 @@ __global__ __launch_bounds__(256) void transform_points_kernel(const double2* pt
     double qx = ax, qy = ay;
     unsigned char ok = 0;
     for (int k = 0; k < max_iter; k++) {
-        const double2 s = sample_f64(f, H, W, qx, qy);
+        const double2 s = sample(qx, qy);
         const double nx = ax + s.x, ny = ay + s.y;
         const double dx = fabs(nx - qx), dy = fabs(ny - qy);
         qx = nx;
@@ -208,11 +219,13 @@ extern "C" int ma_invert_flow(ma_ctx* ctx, const float* flow, int H, int W, int 
     return MA_OK;
 }
 
-extern "C" int ma_transform_points(ma_ctx* ctx, const double* pts, int n, const float* flow, int H, int W, const double* m6,
-                                   const double* t6, int pad_left, int pad_top, int direction, int max_iter, double tol,
-                                   double* out, unsigned char* converged, unsigned char* inside)
+// the checks and the launch that the two point entries share
+template <class S>
+static int transform_points(ma_ctx* ctx, const double* pts, int n, const S& sample, int H, int W, const double* m6,
+                            const double* t6, int pad_left, int pad_top, int direction, int max_iter, double tol,
+                            double* out, unsigned char* converged, unsigned char* inside)
 {
-    MA_REQUIRE(ctx && pts && flow && out && converged && inside, "NULL argument");
+    MA_REQUIRE(ctx && pts && out && converged && inside, "NULL argument");
     MA_REQUIRE(n >= 0, "the number of points must not be negative");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FI_SIDE_MAX && W <= FI_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_REQUIRE(direction == MA_POINTS_TO_MOVING || direction == MA_POINTS_TO_REFERENCE, "unknown direction");
@@ -226,9 +239,30 @@ extern "C" int ma_transform_points(ma_ctx* ctx, const double* pts, int n, const 
     if (a)
         for (int i = 0; i < 6; i++) A.v[i] = a[i];
     MA_HIP(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(transform_points_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const double2*)pts, n, (const float2*)flow, H, W, A, (double)pad_left, (double)pad_top, direction,
+    hipLaunchKernelGGL(transform_points_kernel<S>, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const double2*)pts, n, sample, H, W, A, (double)pad_left, (double)pad_top, direction,
                        max_iter, tol, (double2*)out, converged, inside);
     MA_HIP(hipGetLastError());
     return MA_OK;
+}
+
+extern "C" int ma_transform_points(ma_ctx* ctx, const double* pts, int n, const float* flow, int H, int W, const double* m6,
+                                   const double* t6, int pad_left, int pad_top, int direction, int max_iter, double tol,
+                                   double* out, unsigned char* converged, unsigned char* inside)
+{
+    MA_REQUIRE(flow, "NULL argument");
+    return transform_points(ctx, pts, n, DenseSampler64{(const float2*)flow, H, W}, H, W, m6, t6, pad_left, pad_top, direction,
+                            max_iter, tol, out, converged, inside);
+}
+
+extern "C" int ma_transform_points_grid(ma_ctx* ctx, const double* pts, int n, const float* nodes, int H, int W, int s,
+                                        const double* m6, const double* t6, int pad_left, int pad_top, int direction,
+                                        int max_iter, double tol, double* out, unsigned char* converged,
+                                        unsigned char* inside)
+{
+    MA_REQUIRE(nodes, "NULL argument");
+    MA_REQUIRE(s >= 1, "the stride must be at least 1");
+    MA_REQUIRE(H >= 1 && W >= 1, "flow sides must be in [1, 2^24]");
+    return transform_points(ctx, pts, n, FgSampler64{fg_grid(nodes, H, W, s)}, H, W, m6, t6, pad_left, pad_top, direction,
+                            max_iter, tol, out, converged, inside);
 }

@@ -10,8 +10,14 @@
 // A block covers a 2-D tile of the output, 64 columns by 4 waves x R rows, so that the source footprint stays compact when
 // the matrix rotates; a thread takes R rows of one column and, when every tap of its wave lies inside the image, issues all
 // their loads before the first sum.
+//
+// The flow of a pixel comes from one of two sources (the kernel's SRC): the dense array, or the nodes of a grid flow
+// (include/microaligner_flowgrid.h), evaluated from the block's node patch in LDS (flow_grid_eval.h); everything after
+// f[r] is the same code, so the warp from a grid is the dense warp of the expanded flow bit for bit.
 #include "remap_interp.h"
+#include "flow_grid_eval.h"
 #include "../../include/microaligner_compose.h"
+#include "../../include/microaligner_flowgrid.h"
 
 #include <algorithm>
 
@@ -83,28 +89,50 @@ __device__ __forceinline__ T compose_px(const T* __restrict__ img, const Compose
     }
 }
 
+// the two sources of a pixel's flow
+struct DenseFlow { const float2* __restrict__ p; };   // (H, W)
+struct GridFlow { FgGrid g; };
+
 // Output rows [y_begin, y_end) (the whole image for ma_warp_affine_flow, one band for the page driver).  Block tiles beyond
 // the grid's y extent loop (gridDim.y is capped).  IDX32: the output has fewer than 2^31 elements (so has the image).
-template <typename T, int MODE, bool IDX32>
-__global__ __launch_bounds__(256) void warp_compose_kernel(const T* __restrict__ img, ComposeArgs a,
-                                                           const float2* __restrict__ flow, T* __restrict__ out,
-                                                           int y_begin, int y_end)
+template <typename T, int MODE, bool IDX32, class SRC>
+__global__ __launch_bounds__(256) void warp_compose_kernel(const T* __restrict__ img, ComposeArgs a, SRC src,
+                                                           T* __restrict__ out, int y_begin, int y_end)
 {
     constexpr int N = Compose<MODE>::N, OFF = Compose<MODE>::OFF, R = Compose<MODE>::R, TILE_H = WAVES * R;
+    constexpr bool GRID = std::is_same<SRC, GridFlow>::value;
+    static_assert(TILE_W == FG_TILE_W, "the node patch is as wide as the tile");
     __shared__ float s_tab[TAB * (N > 2 ? N : 1)];
     if constexpr (N > 2) load_tab<N>(s_tab);
     const int x = blockIdx.x * TILE_W + (int)(threadIdx.x & 63);
     const int wave = (int)(threadIdx.x >> 6);
-    if (x >= a.W) return;
+    // with a grid every thread of the block stages the tile's nodes, so none leaves before the barriers
+    if constexpr (!GRID)
+        if (x >= a.W) return;
     for (int yt = y_begin + (int)blockIdx.y * TILE_H; yt < y_end; yt += (int)gridDim.y * TILE_H) {
         const int y0 = yt + wave * R;
-        if (y0 >= y_end) continue;   // wave-uniform
         float2 f[R];
         int ys[R];
+        if constexpr (GRID) {
+            __shared__ FgTile<TILE_H> s_tile;
+            const int bx0 = blockIdx.x * TILE_W;
+            __syncthreads();      // the tile before is read
+            fg_stage(s_tile, src.g, bx0, min(bx0 + TILE_W, a.W), yt, min(yt + TILE_H, y_end), (int)threadIdx.x, 256);
+            __syncthreads();
+            if (x >= a.W || y0 >= y_end) continue;
+            const FgCol col = fg_col(src.g, bx0, x);
 #pragma unroll
-        for (int r = 0; r < R; r++) {
-            ys[r] = min(y0 + r, y_end - 1);
-            f[r] = IDX32 ? flow[(unsigned)ys[r] * (unsigned)a.W + (unsigned)x] : flow[(size_t)ys[r] * a.W + x];
+            for (int r = 0; r < R; r++) {
+                ys[r] = min(y0 + r, y_end - 1);
+                f[r] = fg_eval(s_tile, src.g, col, ys[r] - yt);
+            }
+        } else {
+            if (y0 >= y_end) continue;   // wave-uniform
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                ys[r] = min(y0 + r, y_end - 1);
+                f[r] = IDX32 ? src.p[(unsigned)ys[r] * (unsigned)a.W + (unsigned)x] : src.p[(size_t)ys[r] * a.W + x];
+            }
         }
         T res[R];
         if constexpr (MODE == MA_INTER_NEAREST) {
@@ -195,15 +223,16 @@ ComposeArgs make_args(int h, int w, int pad_left, int pad_top, int H, int W, con
     return a;
 }
 
-// the kernel over output rows [y0, y1) on the ctx stream
-int launch_compose(ma_ctx* ctx, const void* img, int dtype, const ComposeArgs& a, const float2* flow, void* out, int y0,
+// the kernel over output rows [y0, y1) on the ctx stream, the flow from `src`
+template <class SRC>
+int launch_compose(ma_ctx* ctx, const void* img, int dtype, const ComposeArgs& a, const SRC& src, void* out, int y0,
                    int y1, int interp)
 {
     const int th = WAVES * compose_rows(interp);
     const dim3 grid((a.W + TILE_W - 1) / TILE_W, std::min((y1 - y0 + th - 1) / th, MA_GRID_Y_MAX)), block(256);
     const bool idx32 = (unsigned long long)a.H * (unsigned long long)a.W < (1ull << 31);
-#define MA_WC(T, M) do { if (idx32) hipLaunchKernelGGL((warp_compose_kernel<T, M, true>), grid, block, 0, ctx->stream, (const T*)img, a, flow, (T*)out, y0, y1); \
-                         else hipLaunchKernelGGL((warp_compose_kernel<T, M, false>), grid, block, 0, ctx->stream, (const T*)img, a, flow, (T*)out, y0, y1); } while (0)
+#define MA_WC(T, M) do { if (idx32) hipLaunchKernelGGL((warp_compose_kernel<T, M, true, SRC>), grid, block, 0, ctx->stream, (const T*)img, a, src, (T*)out, y0, y1); \
+                         else hipLaunchKernelGGL((warp_compose_kernel<T, M, false, SRC>), grid, block, 0, ctx->stream, (const T*)img, a, src, (T*)out, y0, y1); } while (0)
 #define MA_WC_T(T) do { if (interp == MA_INTER_NEAREST) MA_WC(T, MA_INTER_NEAREST); else if (interp == MA_INTER_LINEAR) MA_WC(T, MA_INTER_LINEAR); \
                         else if (interp == MA_INTER_CUBIC) MA_WC(T, MA_INTER_CUBIC); else MA_WC(T, MA_INTER_LANCZOS4); } while (0)
     if (dtype == MA_U8) MA_WC_T(uint8_t);
@@ -227,20 +256,37 @@ int ma_warp_affine_flow(ma_ctx* ctx, const void* img, int dtype, int h, int w, i
     MA_HIP(hipSetDevice(ctx->device));
     MA_TRY(ensure_tables(ctx));
     MaProfScope ps(ctx, MA_K_OTHER, (double)H * W);
-    return launch_compose(ctx, img, dtype, make_args(h, w, pad_left, pad_top, H, W, m), (const float2*)flow, out, 0, H,
-                          interp);
+    return launch_compose(ctx, img, dtype, make_args(h, w, pad_left, pad_top, H, W, m), DenseFlow{(const float2*)flow}, out,
+                          0, H, interp);
 }
+
+int ma_warp_affine_grid(ma_ctx* ctx, const void* img, int dtype, int h, int w, int pad_left, int pad_top,
+                        const float* nodes, int H, int W, int s, const double m[6], void* out, int interp)
+{
+    MA_TRY(check_args(dtype, h, w, pad_left, pad_top, H, W, m, interp));
+    MA_REQUIRE(ctx && img && nodes && out, "NULL argument");
+    MA_REQUIRE(s >= 1, "the stride must be at least 1");
+    MA_HIP(hipSetDevice(ctx->device));
+    MA_TRY(ensure_tables(ctx));
+    MaProfScope ps(ctx, MA_K_OTHER, (double)H * W);
+    return launch_compose(ctx, img, dtype, make_args(h, w, pad_left, pad_top, H, W, m), GridFlow{fg_grid(nodes, H, W, s)}, out,
+                          0, H, interp);
+}
+
+} // extern "C"
+
+namespace {
 
 // Page driver: the one pipeline (page_pipeline.hip), except that a page goes up whole (without a pass over the flow the
 // source rows an output band reads are not bounded) and only the output is cut into bands, of MA_OPT_WARP_BAND_BYTES and
 // no tile alignment: page i goes up while the bands of page i - 1 are launched, and each band's rows come down as soon as
 // its kernel has run.
-int ma_warp_affine_flow_pages_host(ma_ctx* ctx, const void* const* pages_host, void* const* out_host, int n_pages,
-                                   int dtype, int h, int w, int pad_left, int pad_top, const float* flow, int H, int W,
-                                   const double m[6], int interp)
+template <class SRC>
+int compose_pages(ma_ctx* ctx, const void* const* pages_host, void* const* out_host, int n_pages, int dtype, int h, int w,
+                  int pad_left, int pad_top, const SRC& src, int H, int W, const double m[6], int interp)
 {
     MA_TRY(check_args(dtype, h, w, pad_left, pad_top, H, W, m, interp));
-    MA_REQUIRE(ctx && pages_host && out_host && flow, "NULL argument");
+    MA_REQUIRE(ctx && pages_host && out_host, "NULL argument");
     MA_REQUIRE(n_pages >= 0, "bad page count");
     for (int i = 0; i < n_pages; i++) MA_REQUIRE(pages_host[i] && out_host[i], "NULL page pointer");
     if (n_pages == 0) return MA_OK;
@@ -258,8 +304,32 @@ int ma_warp_affine_flow_pages_host(ma_ctx* ctx, const void* const* pages_host, v
     plan.cuts_src.assign(1, plan.in_bytes);
     for (int y = 0; y < H; y += band_rows) plan.cuts_out.push_back((size_t)std::min(H, y + band_rows) * rowb);
     return ma_warp_pages_run(ctx, pages_host, out_host, n_pages, plan, [&](const void* din, void* dout, int y0, int y1) {
-        return launch_compose(ctx, din, dtype, args, (const float2*)flow, dout, y0, y1, interp);
+        return launch_compose(ctx, din, dtype, args, src, dout, y0, y1, interp);
     });
+}
+
+} // namespace
+
+extern "C" {
+
+int ma_warp_affine_flow_pages_host(ma_ctx* ctx, const void* const* pages_host, void* const* out_host, int n_pages,
+                                   int dtype, int h, int w, int pad_left, int pad_top, const float* flow, int H, int W,
+                                   const double m[6], int interp)
+{
+    MA_REQUIRE(flow, "NULL argument");
+    return compose_pages(ctx, pages_host, out_host, n_pages, dtype, h, w, pad_left, pad_top, DenseFlow{(const float2*)flow}, H,
+                         W, m, interp);
+}
+
+int ma_warp_affine_grid_pages_host(ma_ctx* ctx, const void* const* pages_host, void* const* out_host, int n_pages,
+                                   int dtype, int h, int w, int pad_left, int pad_top, const float* nodes, int H, int W,
+                                   int s, const double m[6], int interp)
+{
+    MA_REQUIRE(nodes, "NULL argument");
+    MA_REQUIRE(s >= 1, "the stride must be at least 1");
+    MA_REQUIRE(H > 0 && W > 0, "empty image");
+    return compose_pages(ctx, pages_host, out_host, n_pages, dtype, h, w, pad_left, pad_top,
+                         GridFlow{fg_grid(nodes, H, W, s)}, H, W, m, interp);
 }
 
 } // extern "C"

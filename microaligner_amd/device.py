@@ -99,8 +99,15 @@ def transform_points_params(points, flow, direction, tmat, image_shape, max_iter
     device: (points as a C-contiguous (N, 2) float64 array, direction code, the 6 doubles of the matrix that direction
     uses or None, pad_left, pad_top, max_iter, tol).  tmat and image_shape are Warper.tmat and the shape of the moving
     image it resamples (default: the flow's (H, W)); the matrix and the padding come from affine_flow_params.
-    ValueError for anything else."""
-    H, W = _check_flow(flow)
+    `flow` may be a FlowGrid.  ValueError for anything else."""
+    if isinstance(flow, FlowGrid):
+        H, W = flow.shape
+        if H > 1 << 24 or W > 1 << 24:
+            raise ValueError(f"flow sides must be in [1, 2^24], got {(H, W)}")
+        flow_shape, flow_dtype = (H, W, 2), np.float32
+    else:
+        H, W = _check_flow(flow)
+        flow_shape, flow_dtype = flow.shape, flow.dtype
     if not isinstance(direction, str) or direction not in POINT_DIRECTIONS:
         raise ValueError(f"unknown direction {direction!r}: expected one of {sorted(POINT_DIRECTIONS)}")
     if not isinstance(points, np.ndarray) or points.dtype != np.float64 or points.ndim != 2 or points.shape[1] != 2:
@@ -117,7 +124,7 @@ def transform_points_params(points, flow, direction, tmat, image_shape, max_iter
             shape = (H, W) if image_shape is None else tuple(int(v) for v in image_shape)
         except (TypeError, ValueError):
             raise ValueError(f"image_shape must be (h, w), got {image_shape!r}") from None
-        _, m, left, top = affine_flow_params(shape, np.float32, flow.shape, flow.dtype, tmat)
+        _, m, left, top = affine_flow_params(shape, np.float32, flow_shape, flow_dtype, tmat)
         mat = m if direction == "to_moving" else np.asarray(tmat, np.float64).ravel()
     return np.ascontiguousarray(points), POINT_DIRECTIONS[direction], mat, left, top, max_iter, tol
 
@@ -202,6 +209,99 @@ class DeviceArray:
             self.free()
         except Exception:
             pass
+
+
+# ---- grid flows (include/microaligner_flowgrid.h) ------------------------------------------------------------------------
+def grid_nodes(n, stride):
+    """g(n, s): the number of nodes of an axis of n pixels at stride s -- 1 for one pixel, else ceil((n - 1) / s) + 1."""
+    return 1 if n == 1 else -(-(n - 1) // stride) + 1
+
+
+def _check_stride(stride):
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= int(stride) < 1 << 31:
+        raise ValueError(f"stride must be an integer in [1, 2^31), got {stride!r}")
+    return int(stride)
+
+
+def _check_grid_shape(shape):
+    try:
+        H, W = shape
+        ok = all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) and 1 <= int(v) <= 1 << 30 for v in (H, W))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"shape must be the flow's (H, W) with sides in [1, 2^30], got {shape!r}")
+    return int(H), int(W)
+
+
+class FlowGrid:
+    """A flow kept as its values on a coarse grid: `nodes` (gh, gw, 2) float32, one node every `stride` pixels of a flow of
+    `shape` (H, W) and one on the last row and column, bilinear interpolation between them
+    (include/microaligner_flowgrid.h).  nodes: a numpy array or a DeviceArray.  ValueError for a wrong dtype, stride or
+    shape, or nodes that are not (g(H, s), g(W, s), 2), before any device work."""
+    FORMAT_VERSION = 1
+
+    def __init__(self, nodes, stride, shape):
+        self.stride, self.shape = _check_stride(stride), _check_grid_shape(shape)
+        want = (grid_nodes(self.shape[0], self.stride), grid_nodes(self.shape[1], self.stride), 2)
+        if not isinstance(nodes, (np.ndarray, DeviceArray)) or nodes.dtype != np.float32 or tuple(nodes.shape) != want:
+            raise ValueError(f"nodes must be a float32 numpy array or DeviceArray of shape {want} for a flow of shape "
+                             f"{self.shape} at stride {self.stride}, got {getattr(nodes, 'dtype', type(nodes))} "
+                             f"{tuple(getattr(nodes, 'shape', ()))}")
+        self.nodes = nodes if isinstance(nodes, DeviceArray) else np.ascontiguousarray(nodes)
+
+    def __len__(self):
+        return self.nodes.shape[0]
+
+    def __repr__(self):
+        return f"FlowGrid(shape={self.shape}, stride={self.stride}, nodes={tuple(self.nodes.shape)})"
+
+    @property
+    def nbytes(self):
+        return int(self.nodes.nbytes)
+
+    def expand(self):
+        """The dense (H, W, 2) float32 flow, evaluated on the device: numpy nodes give numpy, device nodes a DeviceArray."""
+        out = get_context().flow_grid_expand(self)
+        return out if isinstance(self.nodes, DeviceArray) else out.numpy()
+
+    def save(self, path):
+        """Write nodes, stride, shape and the format version to a .npz (numpy appends the suffix if `path` lacks it)."""
+        nodes = self.nodes.numpy() if isinstance(self.nodes, DeviceArray) else self.nodes
+        np.savez(path, nodes=nodes, stride=np.int64(self.stride), shape=np.asarray(self.shape, np.int64),
+                 format_version=np.int64(self.FORMAT_VERSION))
+
+    @classmethod
+    def load(cls, path):
+        """The grid save() wrote (numpy nodes).  ValueError for a file that is not one or has another format version."""
+        with np.load(path, allow_pickle=False) as z:
+            missing = [k for k in ("nodes", "stride", "shape", "format_version") if k not in z.files]
+            if missing:
+                raise ValueError(f"{path} is not a FlowGrid file: {missing} missing")
+            version = int(z["format_version"])
+            if version != cls.FORMAT_VERSION:
+                raise ValueError(f"{path} has FlowGrid format version {version}, this package reads {cls.FORMAT_VERSION}")
+            return cls(z["nodes"], int(z["stride"]), tuple(int(v) for v in z["shape"]))
+
+
+def dense_flow(flow):
+    """The one place a FlowGrid becomes a dense flow for the calls that have no native grid path (invert_flow,
+    compose_flows, flow_qc): expanded on the device, a DeviceArray.  Anything else passes through."""
+    return get_context().flow_grid_expand(flow) if isinstance(flow, FlowGrid) else flow
+
+
+def affine_grid_params(img_shape, img_dtype, grid, tmat, interpolation="linear"):
+    """affine_flow_params for a FlowGrid.  tmat None: the identity and no padding, so the image has the grid's (H, W)."""
+    if not isinstance(grid, FlowGrid):
+        raise ValueError(f"expected a FlowGrid, got {type(grid).__name__}")
+    H, W = grid.shape
+    if tmat is not None:
+        return affine_flow_params(img_shape, img_dtype, (H, W, 2), np.float32, tmat, interpolation)
+    interp = interp_code(interpolation)
+    _dt(img_dtype)
+    if tuple(img_shape) != (H, W):
+        raise ValueError(f"without tmat the image must have the grid's shape {(H, W)}, got {tuple(img_shape)}")
+    return interp, np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0]), 0, 0
 
 
 class _HostBuffer:
@@ -817,6 +917,76 @@ class Context:
                   H, W, (C.c_double * 6)(*[float(v) for v in m]), interp)
         return out
 
+    # grid flows (include/microaligner_flowgrid.h) -------------------------------------------------------------------------
+    def flow_grid_sample(self, flow, stride):
+        """The FlowGrid (device nodes) of a device-resident (H, W, 2) float32 flow at `stride`: point sampling."""
+        H, W = _check_flow(flow)
+        stride = _check_stride(stride)
+        nodes = self.empty((grid_nodes(H, stride), grid_nodes(W, stride), 2), np.float32)
+        self._run(self.lib.ma_flow_grid_sample, flow.ptr, H, W, stride, nodes.ptr)
+        return FlowGrid(nodes, stride, (H, W))
+
+    def _grid_nodes(self, grid, side_max=1 << 24):
+        """the device nodes of a FlowGrid of this context"""
+        if not isinstance(grid, FlowGrid):
+            raise ValueError(f"expected a FlowGrid, got {type(grid).__name__}")
+        if max(grid.shape) > side_max:
+            raise ValueError(f"flow sides must be at most {side_max}, got {grid.shape}")
+        if getattr(grid.nodes, "ctx", self) is not self:
+            raise ValueError("the grid's nodes belong to another context")
+        return self.asdevice(grid.nodes)
+
+    def flow_grid_expand(self, grid):
+        """The dense flow of a FlowGrid as a DeviceArray (H, W, 2)."""
+        nodes = self._grid_nodes(grid)
+        H, W = grid.shape
+        out = self.empty((H, W, 2), np.float32)
+        self._run(self.lib.ma_flow_grid_expand, nodes.ptr, H, W, grid.stride, out.ptr)
+        return out
+
+    def flow_grid_error(self, flow, grid, cell_h, cell_w, tol):
+        """Per cell of the (cell_h, cell_w) grid, what `grid` loses against the device-resident `flow`:
+        (max_err float32, above int64, invalid int64), each (gy, gx) on the host."""
+        H, W = _check_flow(flow)
+        nodes = self._grid_nodes(grid)
+        if grid.shape != (H, W):
+            raise ValueError(f"the grid belongs to a flow of shape {grid.shape}, got {(H, W)}")
+        gy, gx = self._cell_grid_shape(H, W, min(int(cell_h), H), min(int(cell_w), W))
+        max_err = np.empty((gy, gx), np.float32)
+        above, invalid = np.empty((gy, gx), np.int64), np.empty((gy, gx), np.int64)
+        pl = C.POINTER(C.c_longlong)
+        self._run(self.lib.ma_flow_grid_error, flow.ptr, nodes.ptr, H, W, grid.stride, int(cell_h), int(cell_w), float(tol),
+                  max_err.ctypes.data_as(C.POINTER(C.c_float)), above.ctypes.data_as(pl), invalid.ctypes.data_as(pl))
+        return max_err, above, invalid
+
+    def warp_affine_grid(self, img, grid, tmat=None, interpolation="linear"):
+        """warp_affine_flow() with the flow given by a FlowGrid, evaluated from its nodes inside the warp kernel: the
+        result is warp_affine_flow(img, grid.expand(), tmat) bit for bit, and the dense flow is never built.  tmat None: the
+        identity and no padding.  Returns a DeviceArray (H, W)."""
+        interp, m, left, top = affine_grid_params(img.shape, img.dtype, grid, tmat, interpolation)
+        img, nodes = self.asdevice(img), self._grid_nodes(grid, 1 << 30)
+        (h, w), (H, W) = img.shape, grid.shape
+        out = self.empty((H, W), img.dtype)
+        self._run(self.lib.ma_warp_affine_grid, img.ptr, _dt(img.dtype), h, w, left, top, nodes.ptr, H, W, grid.stride,
+                  (C.c_double * 6)(*[float(v) for v in m]), out.ptr, interp)
+        return out
+
+    def warp_affine_grid_pages(self, pages, grid, tmat=None, out=None, interpolation="linear"):
+        """warp_affine_grid() for many HOST pages (h, w) through the page-warp driver of warp_affine_flow_pages(), with
+        the same band plan.  Returns `out`."""
+        pages = [np.ascontiguousarray(p) for p in pages]
+        if not pages:
+            return []
+        interp, m, left, top = affine_grid_params(pages[0].shape, pages[0].dtype, grid, tmat, interpolation)
+        (h, w), (H, W) = pages[0].shape, grid.shape
+        if any(p.shape != (h, w) or p.dtype != pages[0].dtype for p in pages):
+            raise ValueError("all pages must have the same shape and dtype")
+        nodes = self._grid_nodes(grid, 1 << 30)
+        out, n, src, dst = self._page_pointers(pages, out, (H, W), "the flow's (H, W) and the page dtype")
+        self._run(self.lib.ma_warp_affine_grid_pages_host, src, dst, n, _dt(pages[0].dtype), h, w, left, top, nodes.ptr,
+                  H, W, grid.stride, (C.c_double * 6)(*[float(v) for v in m]), interp)
+        return out
+
     def merge_flows(self, flow1, flow2, tile, overlap):
         """_merge_flow_in_tiles (optflow_registrator.py:217-233)."""
         if flow1.shape != flow2.shape:
@@ -866,17 +1036,23 @@ class Context:
         points of the registered frame to the coordinate of the moving image that Warper samples there, "to_reference"
         takes points of the moving image to the registered frame by solving p - flow(p) = tmat . point.  tmat / image_shape:
         Warper.tmat and the shape of the moving image it resamples.  numpy points in and out; flow numpy or device
-        resident.  With return_info a PointsInfo(converged, inside) of bool arrays beside the points."""
+        resident, or a FlowGrid (sampled from its nodes in float64, include/microaligner_flowgrid.h).  With return_info a
+        PointsInfo(converged, inside) of bool arrays beside the points."""
         pts, code, mat, left, top, max_iter, tol = transform_points_params(points, flow, direction, tmat, image_shape,
                                                                            max_iter, tol)
-        flow = self.asdevice(flow)
+        grid = flow if isinstance(flow, FlowGrid) else None
+        flow = self._grid_nodes(grid) if grid is not None else self.asdevice(flow)
         n = pts.shape[0]
-        H, W = flow.shape[:2]
+        H, W = grid.shape if grid is not None else flow.shape[:2]
         d_pts, d_conv, d_in = self._upload_raw(pts), self._raw(n), self._raw(n)
         mat = None if mat is None else (C.c_double * 6)(*[float(v) for v in mat])
         m6, t6 = (mat, None) if code == L.MA_POINTS_TO_MOVING else (None, mat)
-        self._run(self.lib.ma_transform_points, d_pts.ptr, n, flow.ptr, H, W, m6, t6, left, top, code, max_iter, tol,
-                  d_pts.ptr, d_conv.ptr, d_in.ptr)
+        if grid is not None:
+            self._run(self.lib.ma_transform_points_grid, d_pts.ptr, n, flow.ptr, H, W, grid.stride, m6, t6, left, top, code,
+                      max_iter, tol, d_pts.ptr, d_conv.ptr, d_in.ptr)
+        else:
+            self._run(self.lib.ma_transform_points, d_pts.ptr, n, flow.ptr, H, W, m6, t6, left, top, code, max_iter, tol,
+                      d_pts.ptr, d_conv.ptr, d_in.ptr)
         out = self.download_raw(d_pts, (n, 2), np.float64)
         if not return_info:
             return out

@@ -1,4 +1,5 @@
 from .flow_calc import TileFlowCalc, farneback
+from .flow_grid import FlowGrid, FlowGridError, compress_flow, flow_grid_error
 from .flow_invert import invert_flow, transform_points
 from .optflow_registrator import OptFlowRegistrator, compose_flows, merge_two_flows
 from .warper import Warper

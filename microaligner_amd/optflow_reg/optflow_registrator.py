@@ -21,7 +21,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from .. import _lib as L
-from ..device import DeviceArray, get_context
+from ..device import DeviceArray, FlowGrid, dense_flow, get_context
 from ..shared_modules.img_checks import check_img_dims_match, check_img_is_2d_grey, check_img_is_provided
 from ..shared_modules.similarity_scoring import mi_tiled
 from .flow_calc import TileFlowCalc
@@ -41,7 +41,9 @@ def compose_flows(first, second):
     """The flow of "warp by first, then warp the result by second", with warp(img, f)(p) = img(p - f(p)):
     out(p) = second(p) + first sampled at (p - second(p)), linearly, first extended by its border values
     (include/microaligner_flowcompose.h).  Both (H, W, 2) float32 of one shape; numpy in, numpy out; DeviceArray in,
-    DeviceArray out."""
+    DeviceArray out.  A FlowGrid is expanded on the device first (device.dense_flow) and counts as what its nodes are."""
+    like = first.nodes if isinstance(first, FlowGrid) else first
+    first, second = dense_flow(first), dense_flow(second)
     for name, f in (("first", first), ("second", second)):
         if getattr(f, "dtype", None) != np.float32 or len(f.shape) != 3 or f.shape[2] != 2:
             raise ValueError(f"{name} must be an (H, W, 2) float32 flow")
@@ -49,7 +51,7 @@ def compose_flows(first, second):
         raise ValueError(f"flows must have the same shape, got {tuple(first.shape)} and {tuple(second.shape)}")
     ctx = get_context()
     out = ctx.compose_flows(ctx.asdevice(first), ctx.asdevice(second))
-    return out if isinstance(first, DeviceArray) else out.numpy()
+    return out if isinstance(like, DeviceArray) else out.numpy()
 
 
 @dataclass

@@ -10,11 +10,16 @@ With `tmat` set to a 2x3 matrix (FeatureRegistrator.register()'s, the one transf
 the ORIGINAL moving image and is resampled once, through the matrix and the flow together
 (include/microaligner_compose.h): the result has the flow's shape, covers the whole image (tile_size / overlap do not
 apply) and differs from transform_img_with_tmat followed by a plain warp, which interpolates twice.
+
+`flow` may be a FlowGrid (include/microaligner_flowgrid.h): the nodes are evaluated inside that same whole-image warp,
+with `tmat` or, when it is None, the identity and no padding.  This is the whole-image warp of `tmat`, NOT the tiled one
+of a dense flow without a matrix, which zeroes samples beyond a tile's window: the result is
+warp_affine_flow(image, grid.expand(), tmat) bit for bit.
 """
 import numpy as np
 
 from .._lib import MA_INTER_LINEAR as INTER_LINEAR
-from ..device import DeviceArray, affine_flow_params, get_context, interp_code
+from ..device import DeviceArray, FlowGrid, affine_flow_params, affine_grid_params, get_context, interp_code
 
 
 def _mode(interp):
@@ -41,7 +46,7 @@ class Warper:
         if len(self.flow) == 0:
             raise ValueError("No flow provided")
         interp = interp_code(self.interpolation)
-        if self.tmat is not None:
+        if self.tmat is not None or isinstance(self.flow, FlowGrid):
             return self._warp_affine_flow()
         ctx = get_context()
         like = self.image
@@ -70,6 +75,8 @@ class Warper:
         """affine_flow_params of `like` against the flow and tmat: every check before any device work"""
         if np.ndim(like) != 2:
             raise ValueError(f"Expected 2D grayscale image, got shape {np.shape(like)}")
+        if isinstance(self.flow, FlowGrid):
+            return affine_grid_params(np.shape(like), like.dtype, self.flow, self.tmat, self.interpolation)
         return affine_flow_params(np.shape(like), like.dtype, np.shape(self.flow), self.flow.dtype, self.tmat,
                                   self.interpolation)
 
@@ -78,15 +85,19 @@ class Warper:
         self._params(like)
         interp, tmat = interp_code(self.interpolation), self.tmat
         ctx = get_context()
+        # a dense flow or a grid: the same two calls, the resident and the page driver's
+        if isinstance(self.flow, FlowGrid):
+            flow, warp, warp_pages = self.flow, ctx.warp_affine_grid, ctx.warp_affine_grid_pages
+        else:
+            flow, warp, warp_pages = ctx.asdevice(self.flow), ctx.warp_affine_flow, ctx.warp_affine_flow_pages
         if isinstance(like, np.ndarray) and like.nbytes >= self.HOST_BANDED_MIN:
             like = np.ascontiguousarray(like)
         if isinstance(like, np.ndarray) and like.nbytes >= self.HOST_BANDED_MIN and not ctx.is_resident(like):
             # a large host page: the page driver uploads it whole and downloads the result in bands under the kernel
-            flow = ctx.asdevice(self.flow)
             out = ctx.host_empty(flow.shape[:2], like.dtype)
-            ctx.warp_affine_flow_pages([like], flow, tmat, [out], interpolation=interp)
+            warp_pages([like], flow, tmat, [out], interpolation=interp)
         else:
-            out = ctx.warp_affine_flow(ctx.asdevice(like), ctx.asdevice(self.flow), tmat, interpolation=interp)
+            out = warp(ctx.asdevice(like), flow, tmat, interpolation=interp)
             if not isinstance(like, DeviceArray):
                 out = out.numpy()
         # the matrix is consumed with the image and the flow
@@ -102,11 +113,16 @@ class Warper:
         if len(self.flow) == 0:
             raise ValueError("No flow provided")
         interp = interp_code(self.interpolation)
-        if self.tmat is not None:
+        grid = self.flow if isinstance(self.flow, FlowGrid) else None
+        if self.tmat is not None or grid is not None:
             pages = [np.ascontiguousarray(p) for p in pages]
             for p in pages:
                 self._params(p)
         ctx = get_context()
+        if grid is not None:
+            # the nodes stay resident for further calls, as a flow does
+            self.flow = grid = FlowGrid(ctx.asdevice(grid.nodes), grid.stride, grid.shape)
+            return ctx.warp_affine_grid_pages(pages, grid, self.tmat, out, interpolation=interp)
         flow = ctx.asdevice(self.flow)
         self.flow = flow  # stays resident for further calls
         if self.tmat is not None:

@@ -65,6 +65,16 @@ class RegParam:
             if d["FlowComposition"] not in ("reference", "exact"):
                 raise ValueError(f"Field FlowComposition value is not one of: {['reference', 'exact']}")
             self.FlowComposition = d["FlowComposition"]
+        # addition, OptFlowReg only: keep every registered cycle's flow as a FlowGrid of this stride beside the outputs
+        self.SaveFlowGridStride = None
+        if "SaveFlowGridStride" in d:
+            if not optflow:
+                raise ValueError("Field SaveFlowGridStride belongs to OptFlowReg only")
+            _check_dtype("SaveFlowGridStride", int, d)
+            if isinstance(d["SaveFlowGridStride"], bool):
+                raise TypeError("Field SaveFlowGridStride has wrong data type <class 'bool'>, expected an integer")
+            _check_min_max("SaveFlowGridStride", 1, None, d)
+            self.SaveFlowGridStride = d["SaveFlowGridStride"]
         _check_min_max("NumberPyramidLevels", 0, 8, d)
         _check_min_max("NumberIterationsPerLevel", 1, None, d)
         _check_min_max("TileSize", 20, None, d)
@@ -375,8 +385,10 @@ def run_feature_reg(cfg, cycles, log=print):
 
 def run_optflow_reg(cfg, cycles, writer, log=print):
     """run_opt_flow_reg / register_and_save_ofreg_imgs (__main__.py:320-437,532-609): cycle k+1 is registered against the
-    warped reference channel of cycle k (the chain), every page of the cycle is warped with that one flow and written."""
-    from . import OptFlowRegistrator, Warper
+    warped reference channel of cycle k (the chain), every page of the cycle is warped with that one flow and written.
+    With SaveFlowGridStride the flow of every registered cycle is also kept, as
+    <OutputPrefix>optflow_reg_flowgrid_cycNNN.npz (FlowGrid.load reads it)."""
+    from . import OptFlowRegistrator, Warper, compress_flow
     from .shared_modules.utils import max_project_and_normalize
     reg = OptFlowRegistrator()
     for k, v in cfg.optflow.optflow_kwargs().items():
@@ -396,6 +408,12 @@ def run_optflow_reg(cfg, cycles, writer, log=print):
             continue
         reg.ref_img, reg.mov_img = ref_img, mov_img
         flow = reg.register()
+        if cfg.optflow.SaveFlowGridStride is not None:
+            grid, err = compress_flow(flow, stride=cfg.optflow.SaveFlowGridStride, return_error=True)
+            path = cfg.out_dir / f"{cfg.out_prefix}optflow_reg_flowgrid_cyc{cyc:03d}.npz"
+            grid.save(path)
+            log(f"Saved the flow of Cycle {cyc} at stride {grid.stride} to {path.name}: max_err {err.global_max_err:.9g} px, "
+                f"{grid.nbytes} bytes")
         warper.image, warper.flow = mov_img, flow
         ref_img = warper.warp()                      # will be used in the next cycle (:424)
         log(f"Saving Cycle {cyc} [{n + 1}/{len(cycles)}]")

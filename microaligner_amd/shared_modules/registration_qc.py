@@ -15,7 +15,7 @@ from typing import Tuple, Union
 import numpy as np
 
 from .. import _lib as L
-from ..device import DeviceArray, get_context
+from ..device import DeviceArray, dense_flow, get_context
 
 _IMG_DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float32))
 
@@ -129,7 +129,9 @@ def _flow_maps(ctx, flow, ch, cw):
 
 
 def flow_qc(flow, cell_size: Union[int, Tuple[int, int]] = 1000) -> FlowQC:
-    """The flow half of assess_registration(): Jacobian and magnitude statistics per cell, no images."""
+    """The flow half of assess_registration(): Jacobian and magnitude statistics per cell, no images.  A FlowGrid is
+    expanded on the device first (device.dense_flow)."""
+    flow = dense_flow(flow)
     fshape = flow.shape if isinstance(flow, DeviceArray) else np.shape(flow)
     if len(fshape) != 3:
         raise ValueError(f"flow must be float32 of shape (H, W, 2), got shape {tuple(fshape)}")
