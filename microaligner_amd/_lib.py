@@ -196,6 +196,16 @@ FLOWGRID_SIGNATURES = {
                                       _vp]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_flowsmooth.h (weighted smoothing of a flow, fold
+# mask)
+MA_SMOOTH_WEIGHT_NONE, MA_SMOOTH_WEIGHT_F32, MA_SMOOTH_WEIGHT_U8, MA_SMOOTH_WEIGHT_CELLS = 0, 1, 2, 3   # enum ma_smooth_weight_kind
+MA_SMOOTH_ALL, MA_SMOOTH_BLEND = 0, 1                                                                   # enum ma_smooth_mode
+MA_SMOOTH_MAX_RADIUS, MA_FOLD_MASK_MAX_MARGIN = 128, 32
+FLOWSMOOTH_SIGNATURES = {
+    "ma_smooth_flow": (_i, [_vp, _vp, _i, _i, C.POINTER(_f), _i, _vp, _i, _i, _i, _i, _f, _vp, C.POINTER(C.c_longlong)]),
+    "ma_flow_fold_mask": (_i, [_vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_longlong)]),
+}
+
 _lib = None
 
 
@@ -211,7 +221,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + \
             list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()) + list(FLOWINVERT_SIGNATURES.items()) + \
-            list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()):
+            list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()) + list(FLOWSMOOTH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,387 @@
+// Weighted Gaussian smoothing of a flow and the fold mask (include/microaligner_flowsmooth.h).  Off the measured path:
+// nothing in register() or warp() calls it.
+//
+// The smoothing is a separable FIR over the three planes w*u, w*v, w with up to 257 taps, in two launches through a
+// 12 B/px workspace that holds the row pass's planes TRANSPOSED ((W, H) each).  Both passes are then the same tile: 64
+// lines (lanes) x FS_S = FS_NW * FS_R outputs along the filtered axis, which is the fast axis of what the pass reads.
+//   - staging: a wave reads a line's span (outputs + r halo + guards) with consecutive lanes on consecutive elements
+//     (coalesced: float2 flow loads in the row pass, float loads of a transposed plane in the column pass) into
+//     LDS [64 lines][pitch], pitch odd, so that these writes and the filter's reads (lane = line) are free of bank conflicts;
+//   - filter: a thread slides a register window along its line for FS_R consecutive outputs (d_sym_fir_slide_pk, the
+//     window blurs' and DOG's filter), in the accumulation order of the header, one plane after the other through the same
+//     LDS tile;
+//   - output: lane = line, and a line of the input is a column of the output, so the stores are coalesced as well: the row
+//     pass writes its planes transposed, the column pass writes out (and reads flow / weight for the blend) row-major.
+// One kernel family for every r in 1 .. 128: LDS is sized by r at launch (43 KiB at r = 18, 97 KiB at r = 128).
+// Bound by the instructions it issues (two LDS reads and three packed operations per tap and 16 outputs), like the window
+// blurs, not by bytes; at large r the halo (2r staged elements beside 128 outputs per line) adds to it.
+#include "../../include/microaligner_flowsmooth.h"
+#include "cell_grid.h"
+#include "flow_jacobian.h"
+
+#include <cmath>
+#include <vector>
+
+namespace {
+
+constexpr int FS_SIDE_MAX = 1 << 24;
+constexpr int FS_NW = 8, FS_R = 16, FS_S = FS_NW * FS_R;   // waves per block, outputs per thread, outputs per line and block
+constexpr int FS_G = 2;                                     // guard elements either side of the halo (d_sym_fir_slide_pk)
+constexpr int FS_TAPS = 8 + MA_SMOOTH_MAX_RADIUS + 8;       // floats of a tap table in the MA_TAP layout
+
+static inline int fs_span(int r) { return FS_S + 2 * r + 2 * FS_G; }
+static inline int fs_pitch(int r) { return fs_span(r) | 1; }
+
+struct FsTaps { float t[MA_SMOOTH_MAX_RADIUS + 1]; };
+
+struct FsWeight {
+    const void* p;
+    int ch, cw, gx;
+};
+
+__device__ __forceinline__ bool fs_finite(float v) { return fabsf(v) < INFINITY; }
+
+// weight(p) of the header; i = y * W + x
+template <int KIND>
+__device__ __forceinline__ float fs_weight_at(const FsWeight& wt, size_t i, int x, int y)
+{
+    if (KIND == MA_SMOOTH_WEIGHT_F32) return ((const float*)wt.p)[i];
+    if (KIND == MA_SMOOTH_WEIGHT_U8) return ((const unsigned char*)wt.p)[i] ? 1.f : 0.f;
+    if (KIND == MA_SMOOTH_WEIGHT_CELLS) return ((const float*)wt.p)[(size_t)(y / wt.ch) * wt.gx + x / wt.cw];
+    return 1.f;
+}
+
+// the effective weight w(p) of the header
+__device__ __forceinline__ float fs_effective(float wgt, float2 f)
+{
+    return (wgt > 0.f && wgt < INFINITY && fs_finite(f.x) && fs_finite(f.y)) ? wgt : 0.f;
+}
+
+// the header's rule on an axis of n ones at position x: the samples inside the image are 1, the others 0
+__device__ __forceinline__ float fs_rule_of_ones(const FsTaps& taps, int r, int x, int n)
+{
+    float a = taps.t[0] * 1.f;
+    for (int k = 1; k <= r; k++) {
+        const float lo = x - k >= 0 ? 1.f : 0.f, hi = x + k < n ? 1.f : 0.f;
+        a = a + taps.t[k] * (lo + hi);
+    }
+    return a;
+}
+
+// aux[0 .. FS_TAPS): the taps in the MA_TAP layout; with `ones`: aux[FS_TAPS + x] = rs(x), aux[FS_TAPS + W + y] = cs(y)
+__global__ __launch_bounds__(256) void fs_setup_kernel(FsTaps taps, int r, int W, int H, int ones, float* __restrict__ aux)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < FS_TAPS) {
+        float v = 0.f;
+        if (i == 0) v = taps.t[0];
+        else if (i >= 8 && i - 7 <= r) v = taps.t[i - 7];
+        aux[i] = v;
+    }
+    if (!ones) return;
+    if (i < W) aux[FS_TAPS + i] = fs_rule_of_ones(taps, r, (int)i, W);
+    else if (i < (long long)W + H) aux[FS_TAPS + i] = fs_rule_of_ones(taps, r, (int)(i - W), H);
+}
+
+// Row pass.  Block: rows [y0, y0 + 64) x output columns [x0, x0 + FS_S); lane = row.  ws: the three (W, H) planes.
+template <int KIND>
+__global__ __launch_bounds__(64 * FS_NW) void fs_row_kernel(const float2* __restrict__ flow, int H, int W, FsWeight wt, int r,
+                                                            const float* __restrict__ taps, int nbx, float* __restrict__ ws)
+{
+    extern __shared__ float lds[];   // [64][pitch]
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int span = FS_S + 2 * r + 2 * FS_G, pitch = span | 1;
+    const int x0 = (int)(blockIdx.x % nbx) * FS_S, y0 = (int)(blockIdx.x / nbx) * 64;
+    const size_t plane = (size_t)H * W;
+    for (int p = 0; p < 3; p++) {
+        for (int row = wv; row < 64; row += FS_NW) {
+            const int y = y0 + row;
+            float* line = lds + row * pitch;
+            for (int c = lane; c < span; c += 64) {
+                const int x = x0 - r - FS_G + c;
+                float val = 0.f;
+                if (y < H && x >= 0 && x < W) {
+                    const size_t i = (size_t)y * W + x;
+                    const float2 f = flow[i];
+                    const float w = fs_effective(fs_weight_at<KIND>(wt, i, x, y), f);
+                    val = p == 2 ? w : (w > 0.f ? w * (p == 0 ? f.x : f.y) : 0.f);
+                }
+                line[c] = val;
+            }
+        }
+        __syncthreads();
+        float acc[FS_R];
+        d_sym_fir_slide_pk<FS_R, false, false>(lds + lane * pitch, FS_G + r + wv * FS_R, r, taps, acc);
+        __syncthreads();
+        const int y = y0 + lane;
+        float* dst = ws + p * plane;
+#pragma unroll
+        for (int q = 0; q < FS_R; q++) {
+            const int x = x0 + wv * FS_R + q;
+            if (x < W && y < H) dst[(size_t)x * H + y] = acc[q];
+        }
+    }
+}
+
+// Column pass with the divide and the blend.  Block: columns [x0, x0 + 64) x output rows [y0, y0 + FS_S); lane = column.
+// flow and out may be one array: neither is __restrict__, and a thread reads flow only at the pixel it writes.
+template <int KIND, int MODE>
+__global__ __launch_bounds__(64 * FS_NW) void fs_col_kernel(const float* __restrict__ ws, int H, int W, const float2* flow,
+                                                            FsWeight wt, int r, const float* __restrict__ aux, int nbx,
+                                                            float min_support, float2* out,
+                                                            unsigned long long* __restrict__ unsupported)
+{
+    extern __shared__ float lds[];   // [64][pitch]
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int span = FS_S + 2 * r + 2 * FS_G, pitch = span | 1;
+    const int x0 = (int)(blockIdx.x % nbx) * 64, y0 = (int)(blockIdx.x / nbx) * FS_S;
+    const size_t plane = (size_t)H * W;
+    float S[3][FS_R];
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        const float* src = ws + p * plane;
+        for (int row = wv; row < 64; row += FS_NW) {
+            const int x = x0 + row;
+            float* line = lds + row * pitch;
+            for (int c = lane; c < span; c += 64) {
+                const int y = y0 - r - FS_G + c;
+                line[c] = (x < W && y >= 0 && y < H) ? src[(size_t)x * H + y] : 0.f;
+            }
+        }
+        __syncthreads();
+        d_sym_fir_slide_pk<FS_R, false, false>(lds + lane * pitch, FS_G + r + wv * FS_R, r, aux, S[p]);
+        __syncthreads();
+    }
+    const int x = x0 + lane;
+    unsigned int missed = 0;
+    const float rs = (MODE == MA_SMOOTH_BLEND && x < W) ? aux[FS_TAPS + x] : 1.f;
+#pragma unroll
+    for (int q = 0; q < FS_R; q++) {
+        const int y = y0 + wv * FS_R + q;
+        if (x >= W || y >= H) continue;
+        const size_t i = (size_t)y * W + x;
+        const float s2 = S[2][q];
+        float2 s = make_float2(NAN, NAN);
+        if (s2 > min_support) s = make_float2(__fdiv_rn(S[0][q], s2), __fdiv_rn(S[1][q], s2));
+        else missed++;
+        if (MODE == MA_SMOOTH_BLEND) {
+            const float2 f = flow[i];
+            const float w = fs_effective(fs_weight_at<KIND>(wt, i, x, y), f);
+            if (w > 0.f) {
+                const float sn = aux[FS_TAPS + W + y] * rs;
+                const float c = __fdiv_rn(s2, sn);
+                const float d = 4.f * c - 2.f;
+                const float a = d > 0.f ? (d < 1.f ? d : 1.f) : 0.f;
+                if (a == 1.f) s = f;
+                else s = make_float2(s.x + a * (f.x - s.x), s.y + a * (f.y - s.y));
+            }
+        }
+        out[i] = s;
+    }
+    if (unsupported) {     // wave-uniform; one integer add per wave, so the total does not depend on the order
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) missed += __shfl_down(missed, off, 64);
+        if (lane == 0 && missed) atomicAdd(unsupported, (unsigned long long)missed);
+    }
+}
+
+// ---- fold mask ------------------------------------------------------------------------------------------------------------
+// bad(p) of the header as a byte map, and the folded / invalid counts (counts[0], counts[1]).  One pixel per thread; the
+// stencil's four neighbours come from the caches.
+__global__ __launch_bounds__(256) void fs_bad_kernel(const float2* __restrict__ flow, int H, int W, int nbx,
+                                                     unsigned char* __restrict__ bad, unsigned long long* __restrict__ counts)
+{
+    const int x = (int)(blockIdx.x % nbx) * 256 + threadIdx.x;
+    const int y = (int)(blockIdx.x / nbx);
+    unsigned int folded = 0, invalid = 0;
+    if (x < W) {
+        const size_t i = (size_t)y * W + x;
+        const float2 f = flow[i];
+        const double det = ma_flow_det_j([&](int dx, int dy) { return flow[(size_t)(y + dy) * W + (x + dx)]; }, x, y, W, H);
+        folded = ma_finite(det) && det <= 0.0;
+        invalid = !(fs_finite(f.x) && fs_finite(f.y));
+        bad[i] = (folded | invalid) ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        folded += __shfl_down(folded, off, 64);
+        invalid += __shfl_down(invalid, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (folded) atomicAdd(counts, (unsigned long long)folded);
+        if (invalid) atomicAdd(counts + 1, (unsigned long long)invalid);
+    }
+}
+
+// keep = 1 - (bad dilated by the (2 margin + 1)^2 box), separably through LDS: the bad bytes of the tile and its margin,
+// then their OR along x, then along y.  counts[2] = pixels with keep == 0.
+constexpr int FM_TW = 64, FM_TH = 32, FM_M = MA_FOLD_MASK_MAX_MARGIN;
+__global__ __launch_bounds__(256) void fs_dilate_kernel(const unsigned char* __restrict__ bad, int H, int W, int margin, int nbx,
+                                                        unsigned char* __restrict__ keep, unsigned long long* __restrict__ counts)
+{
+    __shared__ unsigned char sb[FM_TH + 2 * FM_M][FM_TW + 2 * FM_M];
+    __shared__ unsigned char sh[FM_TH + 2 * FM_M][FM_TW];
+    const int x0 = (int)(blockIdx.x % nbx) * FM_TW, y0 = (int)(blockIdx.x / nbx) * FM_TH;
+    const int rows = FM_TH + 2 * margin, cols = FM_TW + 2 * margin;
+    for (int t = threadIdx.x; t < rows * cols; t += 256) {
+        const int j = t / cols, c = t - j * cols;
+        const int y = y0 - margin + j, x = x0 - margin + c;
+        sb[j][c] = (y >= 0 && y < H && x >= 0 && x < W) ? bad[(size_t)y * W + x] : 0;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < rows * FM_TW; t += 256) {
+        const int j = t / FM_TW, c = t - j * FM_TW;
+        unsigned char any = 0;
+        for (int d = 0; d <= 2 * margin; d++) any |= sb[j][c + d];
+        sh[j][c] = any;
+    }
+    __syncthreads();
+    unsigned int dropped = 0;
+    for (int t = threadIdx.x; t < FM_TH * FM_TW; t += 256) {
+        const int j = t / FM_TW, c = t - j * FM_TW;
+        const int y = y0 + j, x = x0 + c;
+        unsigned char any = 0;
+        for (int d = 0; d <= 2 * margin; d++) any |= sh[j + d][c];
+        if (y < H && x < W) {
+            keep[(size_t)y * W + x] = any ? 0 : 1;
+            dropped += any ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) dropped += __shfl_down(dropped, off, 64);
+    if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(counts + 2, (unsigned long long)dropped);
+}
+
+// blocks of a 1-D grid over nbx x nby tiles
+static int fs_grid(long long nbx, long long nby, unsigned* blocks)
+{
+    MA_REQUIRE(nbx * nby <= 0x7fffffffLL, "flow too large");
+    *blocks = (unsigned)(nbx * nby);
+    return MA_OK;
+}
+
+template <int KIND>
+static int fs_launch(ma_ctx* ctx, const float* flow, int H, int W, const FsWeight& wt, int r, int mode, float min_support,
+                     const float* aux, float* ws, float* out, unsigned long long* counter)
+{
+    const size_t lds = (size_t)64 * fs_pitch(r) * sizeof(float);
+    const int nbx1 = (W + FS_S - 1) / FS_S, nbx2 = (W + 63) / 64;
+    unsigned g1, g2;
+    MA_TRY(fs_grid(nbx1, (H + 63) / 64, &g1));
+    MA_TRY(fs_grid(nbx2, (H + FS_S - 1) / FS_S, &g2));
+    const void* row = reinterpret_cast<const void*>(fs_row_kernel<KIND>);
+    const void* col = mode == MA_SMOOTH_BLEND ? reinterpret_cast<const void*>(fs_col_kernel<KIND, MA_SMOOTH_BLEND>)
+                                              : reinterpret_cast<const void*>(fs_col_kernel<KIND, MA_SMOOTH_ALL>);
+    if (lds > 64 * 1024) {
+        MA_HIP(hipFuncSetAttribute(row, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MA_HIP(hipFuncSetAttribute(col, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    hipLaunchKernelGGL(fs_row_kernel<KIND>, dim3(g1), dim3(64 * FS_NW), lds, ctx->stream, (const float2*)flow, H, W, wt, r, aux,
+                       nbx1, ws);
+    if (mode == MA_SMOOTH_BLEND)
+        hipLaunchKernelGGL((fs_col_kernel<KIND, MA_SMOOTH_BLEND>), dim3(g2), dim3(64 * FS_NW), lds, ctx->stream, (const float*)ws,
+                           H, W, (const float2*)flow, wt, r, aux, nbx2, min_support, (float2*)out, counter);
+    else
+        hipLaunchKernelGGL((fs_col_kernel<KIND, MA_SMOOTH_ALL>), dim3(g2), dim3(64 * FS_NW), lds, ctx->stream, (const float*)ws,
+                           H, W, (const float2*)flow, wt, r, aux, nbx2, min_support, (float2*)out, counter);
+    MA_HIP(hipGetLastError());
+    return MA_OK;
+}
+
+// the device counters of a call (n of them, zeroed) in the ctx workspace, if the caller asked for counts
+static int fs_counters(ma_ctx* ctx, bool wanted, int n, unsigned long long** counter)
+{
+    *counter = nullptr;
+    if (!wanted) return MA_OK;
+    MA_TRY(ma_ws_reserve(ctx, n * sizeof(unsigned long long)));
+    MA_TRY(ma_pinned_reserve(ctx, n * sizeof(unsigned long long)));
+    *counter = (unsigned long long*)ctx->ws;
+    MA_HIP(hipMemsetAsync(*counter, 0, n * sizeof(unsigned long long), ctx->stream));
+    return MA_OK;
+}
+
+static int fs_read_counters(ma_ctx* ctx, const unsigned long long* counter, int n, long long* host)
+{
+    MA_HIP(hipMemcpyAsync(ctx->pinned, counter, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    MA_HIP(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; k++) host[k] = (long long)((const unsigned long long*)ctx->pinned)[k];
+    return MA_OK;
+}
+
+} // namespace
+
+extern "C" int ma_smooth_flow(ma_ctx* ctx, const float* flow, int H, int W, const float* taps_host, int r, const void* weight,
+                              int weight_kind, int cell_h, int cell_w, int mode, float min_support, float* out,
+                              long long* unsupported_host)
+{
+    MA_REQUIRE(ctx && flow && taps_host && out, "NULL argument");
+    MA_REQUIRE(H >= 1 && W >= 1 && H <= FS_SIDE_MAX && W <= FS_SIDE_MAX, "flow sides must be in [1, 2^24]");
+    MA_REQUIRE(r >= 1 && r <= MA_SMOOTH_MAX_RADIUS, "r must be in [1, 128]");
+    MA_REQUIRE(weight_kind >= MA_SMOOTH_WEIGHT_NONE && weight_kind <= MA_SMOOTH_WEIGHT_CELLS, "unknown weight kind");
+    MA_REQUIRE(mode == MA_SMOOTH_ALL || mode == MA_SMOOTH_BLEND, "unknown mode");
+    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight, "NULL weight");
+    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight != (const void*)out, "weight and out must be distinct arrays");
+    MA_REQUIRE(weight_kind != MA_SMOOTH_WEIGHT_CELLS || (cell_h >= 1 && cell_w >= 1), "cell size must be >= 1");
+    MA_REQUIRE(std::isfinite(min_support) && min_support >= 0.f, "min_support must be finite and not negative");
+    FsTaps taps{};
+    for (int k = 0; k <= r; k++) {
+        MA_REQUIRE(std::isfinite(taps_host[k]) && taps_host[k] >= 0.f, "taps must be finite and not negative");
+        taps.t[k] = taps_host[k];
+    }
+    MA_REQUIRE(taps.t[0] > 0.f, "the centre tap must be positive");
+    MA_HIP(hipSetDevice(ctx->device));
+    unsigned long long* counter;
+    MA_TRY(fs_counters(ctx, unsupported_host != nullptr, 1, &counter));
+    const int ones = mode == MA_SMOOTH_BLEND ? 1 : 0;
+    const size_t aux_n = (size_t)FS_TAPS + (ones ? (size_t)W + H : 0);
+    float* aux = (float*)ma_pool_alloc(ctx, aux_n * sizeof(float));
+    if (!aux) return MA_ENOMEM;
+    float* ws = (float*)ma_pool_alloc(ctx, (size_t)H * W * 3 * sizeof(float));
+    if (!ws) {
+        ma_pool_free(ctx, aux);
+        return MA_ENOMEM;
+    }
+    FsWeight wt{weight, 1, 1, 1};
+    if (weight_kind == MA_SMOOTH_WEIGHT_CELLS) wt = FsWeight{weight, cell_h, cell_w, (int)(((long long)W + cell_w - 1) / cell_w)};
+    hipLaunchKernelGGL(fs_setup_kernel, dim3((unsigned)((aux_n + 255) / 256)), dim3(256), 0, ctx->stream, taps, r, W, H, ones, aux);
+    int rc;
+    switch (weight_kind) {
+    case MA_SMOOTH_WEIGHT_F32: rc = fs_launch<MA_SMOOTH_WEIGHT_F32>(ctx, flow, H, W, wt, r, mode, min_support, aux, ws, out, counter); break;
+    case MA_SMOOTH_WEIGHT_U8: rc = fs_launch<MA_SMOOTH_WEIGHT_U8>(ctx, flow, H, W, wt, r, mode, min_support, aux, ws, out, counter); break;
+    case MA_SMOOTH_WEIGHT_CELLS: rc = fs_launch<MA_SMOOTH_WEIGHT_CELLS>(ctx, flow, H, W, wt, r, mode, min_support, aux, ws, out, counter); break;
+    default: rc = fs_launch<MA_SMOOTH_WEIGHT_NONE>(ctx, flow, H, W, wt, r, mode, min_support, aux, ws, out, counter); break;
+    }
+    // stream-ordered reuse: the next call on this ctx that takes the buffers runs behind these kernels
+    ma_pool_free(ctx, ws);
+    ma_pool_free(ctx, aux);
+    MA_TRY(rc);
+    if (unsupported_host) MA_TRY(fs_read_counters(ctx, counter, 1, unsupported_host));
+    return MA_OK;
+}
+
+extern "C" int ma_flow_fold_mask(ma_ctx* ctx, const float* flow, int H, int W, int margin, unsigned char* keep,
+                                 long long* counts_host)
+{
+    MA_REQUIRE(ctx && flow && keep, "NULL argument");
+    MA_REQUIRE(H >= 1 && W >= 1 && H <= FS_SIDE_MAX && W <= FS_SIDE_MAX, "flow sides must be in [1, 2^24]");
+    MA_REQUIRE(margin >= 0 && margin <= MA_FOLD_MASK_MAX_MARGIN, "margin must be in [0, 32]");
+    const int nbx1 = (W + 255) / 256, nbx2 = (W + FM_TW - 1) / FM_TW;
+    unsigned g1, g2;
+    MA_TRY(fs_grid(nbx1, H, &g1));
+    MA_TRY(fs_grid(nbx2, (H + FM_TH - 1) / FM_TH, &g2));
+    MA_HIP(hipSetDevice(ctx->device));
+    // the counters are always kept on the device (the kernels add to them); read back only on request
+    unsigned long long* counter;
+    MA_TRY(fs_counters(ctx, true, 3, &counter));
+    unsigned char* bad = (unsigned char*)ma_pool_alloc(ctx, (size_t)H * W);
+    if (!bad) return MA_ENOMEM;
+    hipLaunchKernelGGL(fs_bad_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const float2*)flow, H, W, nbx1, bad, counter);
+    hipLaunchKernelGGL(fs_dilate_kernel, dim3(g2), dim3(256), 0, ctx->stream, (const unsigned char*)bad, H, W, margin, nbx2, keep,
+                       counter);
+    ma_pool_free(ctx, bad);
+    MA_HIP(hipGetLastError());
+    if (counts_host) MA_TRY(fs_read_counters(ctx, counter, 3, counts_host));
+    return MA_OK;
+}

@@ -5,6 +5,7 @@
 // 256 x 256 joint histogram, the same f64 formula in the same reduction order, so a cell gives the bits ma_nmi_u8 gives for
 // the cropped cell.
 #include "cell_grid.h"
+#include "flow_jacobian.h"
 #include "nmi_score.h"
 #include "../../include/microaligner_qc.h"
 
@@ -184,27 +185,14 @@ __global__ __launch_bounds__(QF_T) void qc_flow_tile_kernel(const float* __restr
         for (int x = x0 + threadIdx.x; x < x1; x += QF_T) {
             const int c = x - x0 + 1;
             const double u = uc[c], v = vc[c];
-            // numpy.gradient, edge_order=1: central differences / 2 inside, one-sided at the edges, 0 along a unit axis
-            double dudx = 0.0, dvdx = 0.0, dudy = 0.0, dvdy = 0.0;
-            if (W > 1) {
-                if (x == 0)          { dudx = __dsub_rn((double)uc[c + 1], u); dvdx = __dsub_rn((double)vc[c + 1], v); }
-                else if (x == W - 1) { dudx = __dsub_rn(u, (double)uc[c - 1]); dvdx = __dsub_rn(v, (double)vc[c - 1]); }
-                else {
-                    dudx = __dsub_rn((double)uc[c + 1], (double)uc[c - 1]) / 2.0;
-                    dvdx = __dsub_rn((double)vc[c + 1], (double)vc[c - 1]) / 2.0;
-                }
-            }
-            if (H > 1) {
-                if (y == 0)          { dudy = __dsub_rn((double)up[c], u); dvdy = __dsub_rn((double)vp[c], v); }
-                else if (y == H - 1) { dudy = __dsub_rn(u, (double)um[c]); dvdy = __dsub_rn(v, (double)vm[c]); }
-                else {
-                    dudy = __dsub_rn((double)up[c], (double)um[c]) / 2.0;
-                    dvdy = __dsub_rn((double)vp[c], (double)vm[c]) / 2.0;
-                }
-            }
-            const double det = __dsub_rn(__dmul_rn(__dadd_rn(1.0, dudx), __dadd_rn(1.0, dvdy)), __dmul_rn(dudy, dvdx));
-            // det is finite exactly when every value its stencil reads is: finite f32 values give finite differences and
-            // products in f64, and a non-finite operand of +, -, * never yields a finite result
+            // det J of flow_jacobian.h from the three LDS rows
+            const double det = ma_flow_det_j(
+                [&](int dx, int dy) {
+                    const float* ur = dy < 0 ? um : (dy > 0 ? up : uc);
+                    const float* vr = dy < 0 ? vm : (dy > 0 ? vp : vc);
+                    return make_float2(ur[c + dx], vr[c + dx]);
+                },
+                x, y, W, H);
             if (ma_finite(det)) {
                 acc.jmin = fmin(acc.jmin, det);
                 acc.folded += det <= 0.0;

@@ -129,6 +129,108 @@ def transform_points_params(points, flow, direction, tmat, image_shape, max_iter
     return np.ascontiguousarray(points), POINT_DIRECTIONS[direction], mat, left, top, max_iter, tol
 
 
+# ---- smoothing a flow, fold mask (include/microaligner_flowsmooth.h) -------------------------------------------------------
+SMOOTH_MODES = {"all": L.MA_SMOOTH_ALL, "blend": L.MA_SMOOTH_BLEND}
+
+
+def _real(v, name):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name} must be a number, got {v!r}")
+    return float(v)
+
+
+def gaussian_taps(sigma, truncate=3.0):
+    """The taps t[0 .. r] of smooth_flow(): r = max(1, ceil(truncate * sigma)), t_k = exp(-k^2 / (2 sigma^2)) in float64,
+    divided by t_0 + 2 sum(t_k), then rounded to float32.  ValueError for a sigma or truncate that is not finite and
+    positive, or r > 128."""
+    sigma, truncate = _real(sigma, "sigma"), _real(truncate, "truncate")
+    if not (np.isfinite(sigma) and sigma > 0 and np.isfinite(truncate) and truncate > 0):
+        raise ValueError(f"sigma and truncate must be finite and positive, got {sigma!r}, {truncate!r}")
+    rr = np.ceil(truncate * sigma)
+    if not rr <= L.MA_SMOOTH_MAX_RADIUS:
+        raise ValueError(f"r = ceil(truncate * sigma) = {rr:.0f} exceeds {L.MA_SMOOTH_MAX_RADIUS}: smooth in rounds, or lower "
+                         "truncate")
+    k = np.arange(max(1, int(rr)) + 1, dtype=np.float64)
+    t = np.exp(-k * k / (2.0 * sigma ** 2))
+    return (t / (t[0] + 2.0 * t[1:].sum())).astype(np.float32)
+
+
+def _cell_size_hw(cell_size):
+    try:
+        ch, cw = (cell_size, cell_size) if isinstance(cell_size, (int, np.integer)) else cell_size
+        ok = all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) and 1 <= int(v) < 1 << 31 for v in (ch, cw))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"cell_size must be a positive integer or a pair of them, got {cell_size!r}")
+    return int(ch), int(cw)
+
+
+def smooth_flow_params(flow, taps, weight=None, cell_size=None, where="all", min_support=0.0):
+    """Checks and host-side arguments of the weighted smoothing (include/microaligner_flowsmooth.h) without touching a
+    device: (H, W, taps as C-contiguous float32, r, weight kind, cell_h, cell_w, mode, min_support as float32).
+    weight: None; an (H, W) float32 or uint8 array (numpy or device); or, with cell_size, a (gy, gx) float32 map on that
+    cell grid.  ValueError for anything the C entry would refuse."""
+    H, W = _check_flow(flow)
+    if not isinstance(taps, np.ndarray) or taps.dtype != np.float32 or taps.ndim != 1:
+        raise ValueError("taps must be a 1-D float32 numpy array t[0 .. r]")
+    r = taps.shape[0] - 1
+    if not 1 <= r <= L.MA_SMOOTH_MAX_RADIUS:
+        raise ValueError(f"r must be in [1, {L.MA_SMOOTH_MAX_RADIUS}], got {r}")
+    if not (np.all(np.isfinite(taps)) and np.all(taps >= 0) and taps[0] > 0):
+        raise ValueError("taps must be finite and not negative, the centre tap positive")
+    if not isinstance(where, str) or where not in SMOOTH_MODES:
+        raise ValueError(f"unknown mode {where!r}: expected one of {sorted(SMOOTH_MODES)}")
+    ms = _real(min_support, "min_support")
+    with np.errstate(over="ignore"):
+        ms = np.float32(ms)
+    if not (np.isfinite(ms) and ms >= 0):
+        raise ValueError(f"min_support must be finite and not negative as float32, got {min_support!r}")
+    kind, ch, cw = L.MA_SMOOTH_WEIGHT_NONE, 1, 1
+    if weight is None:
+        if cell_size is not None:
+            raise ValueError("cell_size only has a meaning together with a per-cell weight")
+    else:
+        wshape, wdtype = tuple(getattr(weight, "shape", ())), getattr(weight, "dtype", None)
+        if not isinstance(weight, (np.ndarray, DeviceArray)):
+            raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
+        if cell_size is not None:
+            ch, cw = _cell_size_hw(cell_size)
+            want = (-(-H // ch), -(-W // cw))
+            if wdtype != np.float32 or wshape != want:
+                raise ValueError(f"a per-cell weight of cells {(ch, cw)} must be float32 of shape {want}, got {wdtype} {wshape}")
+            kind = L.MA_SMOOTH_WEIGHT_CELLS
+        elif wshape == (H, W) and wdtype == np.float32:
+            kind = L.MA_SMOOTH_WEIGHT_F32
+        elif wshape == (H, W) and wdtype == np.uint8:
+            kind = L.MA_SMOOTH_WEIGHT_U8
+        else:
+            raise ValueError(f"a per-pixel weight must be float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+    return H, W, np.ascontiguousarray(taps), int(r), kind, ch, cw, SMOOTH_MODES[where], float(ms)
+
+
+def fold_mask_params(flow, margin):
+    """Checks of the fold mask (include/microaligner_flowsmooth.h) without touching a device: (H, W, margin)."""
+    H, W = _check_flow(flow)
+    if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or not 0 <= int(margin) <= L.MA_FOLD_MASK_MAX_MARGIN:
+        raise ValueError(f"margin must be an integer in [0, {L.MA_FOLD_MASK_MAX_MARGIN}], got {margin!r}")
+    return H, W, int(margin)
+
+
+class SmoothInfo(collections.namedtuple("SmoothInfo", "unsupported")):
+    """smooth_flow(..., return_info=True): the number of pixels whose smoothed value had no support (S2 <= min_support)."""
+
+
+class FoldInfo(collections.namedtuple("FoldInfo", "folded invalid dropped")):
+    """fold_mask(..., return_info=True): pixels with a finite det J <= 0, pixels with a non-finite component (the sums of
+    flow_qc's maps), and pixels the mask drops (keep == 0)."""
+
+
+class RepairInfo(collections.namedtuple("RepairInfo", "rounds converged")):
+    """repair_flow(..., return_info=True): (folded, invalid, dropped, unsupported) of every smoothing round, and whether
+    the loop ended on a flow with nothing folded and nothing invalid."""
+
+
 class InvertInfo(collections.namedtuple("InvertInfo", "not_converged residual")):
     """invert_flow(..., return_info=True): the number of pixels that took max_iter steps without stopping, and the (H, W)
     float32 size of every pixel's last step (NaN where it was NaN)."""
@@ -1029,6 +1131,33 @@ class Context:
         residual, count = self.empty((H, W), np.float32), C.c_longlong(0)
         self._run(self.lib.ma_invert_flow, flow.ptr, H, W, max_iter, tol, out.ptr, residual.ptr, C.byref(count))
         return out, InvertInfo(int(count.value), residual)
+
+    def smooth_flow(self, flow, taps, weight=None, cell_size=None, where="all", min_support=0.0, return_info=False, out=None):
+        """The weighted smoothing of a flow with the symmetric kernel taps t[0 .. r] (include/microaligner_flowsmooth.h): a
+        row pass and a column pass over w*u, w*v, w, the divide, and for where="blend" the feathering back into the
+        untouched flow.  Device arrays in (weight: None, an (H, W) float32 or uint8 array, or with cell_size a (gy, gx)
+        float32 map), a new device array out; `out` may name the array to write instead, `flow` itself included.  With
+        return_info a SmoothInfo(unsupported) beside it, at the cost of a synchronisation."""
+        H, W, taps, r, kind, ch, cw, mode, ms = smooth_flow_params(flow, taps, weight, cell_size, where, min_support)
+        if out is None:
+            out = self.empty((H, W, 2), np.float32)
+        elif not isinstance(out, DeviceArray) or out.dtype != np.float32 or out.shape != (H, W, 2):
+            raise ValueError(f"out must be a float32 DeviceArray of shape {(H, W, 2)}")
+        count = C.c_longlong(0)
+        self._run(self.lib.ma_smooth_flow, flow.ptr, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r,
+                  None if weight is None else weight.ptr, kind, ch, cw, mode, ms, out.ptr,
+                  C.byref(count) if return_info else None)
+        return (out, SmoothInfo(int(count.value))) if return_info else out
+
+    def fold_mask(self, flow, margin=2, return_info=False):
+        """keep (H, W) uint8: 0 within `margin` pixels (Chebyshev) of a pixel where the flow folds (det J <= 0) or is not
+        finite, else 1 (include/microaligner_flowsmooth.h).  A device array in, a new device array out; with return_info a
+        FoldInfo(folded, invalid, dropped) beside it, at the cost of a synchronisation."""
+        H, W, margin = fold_mask_params(flow, margin)
+        keep = self.empty((H, W), np.uint8)
+        counts = (C.c_longlong * 3)()
+        self._run(self.lib.ma_flow_fold_mask, flow.ptr, H, W, margin, keep.ptr, counts if return_info else None)
+        return (keep, FoldInfo(*(int(v) for v in counts))) if return_info else keep
 
     def transform_points(self, points, flow, direction, tmat=None, image_shape=None, max_iter=50, tol=1e-4,
                          return_info=False):
