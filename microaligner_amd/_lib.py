@@ -206,6 +206,14 @@ FLOWSMOOTH_SIGNATURES = {
     "ma_flow_fold_mask": (_i, [_vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_flowaffine.h (affine moments of a flow, a flow
+# relative to a matrix)
+MA_FLOW_AFFINE_SUMS, MA_FLOW_AFFINE_COUNTS = 14, 4
+FLOWAFFINE_SIGNATURES = {
+    "ma_flow_affine_moments": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, C.POINTER(_d), _d, C.POINTER(_d), C.POINTER(C.c_longlong)]),
+    "ma_flow_affine_apply": (_i, [_vp, _vp, _i, _i, C.POINTER(_d), _vp]),
+}
+
 _lib = None
 
 
@@ -221,7 +229,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + \
             list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()) + list(FLOWINVERT_SIGNATURES.items()) + \
-            list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()) + list(FLOWSMOOTH_SIGNATURES.items()):
+            list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()) + list(FLOWSMOOTH_SIGNATURES.items()) + \
+            list(FLOWAFFINE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

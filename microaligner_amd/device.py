@@ -217,6 +217,61 @@ def fold_mask_params(flow, margin):
     return H, W, int(margin)
 
 
+# ---- affine part of a flow (include/microaligner_flowaffine.h) -------------------------------------------------------------
+def flow_affine_moments_params(flow, weight=None, cell_size=None, prior=None, clip=None):
+    """Checks and host-side arguments of the affine moments (include/microaligner_flowaffine.h) without touching a device:
+    (H, W, weight kind, cell_h, cell_w, prior as 6 float64 or None, clip).  cell_size None: one cell, the whole image.
+    weight: None; an (H, W) float32 or uint8 array (numpy or device); or, with cell_size, a (gy, gx) float32 map on that
+    cell grid.  prior: a finite 2 x 3 matrix in the centred frame, with clip > 0.  ValueError for anything the C entry would
+    refuse."""
+    H, W = _check_flow(flow)
+    ch, cw = (H, W) if cell_size is None else _cell_size_hw(cell_size)
+    kind = L.MA_SMOOTH_WEIGHT_NONE
+    if weight is not None:
+        wshape, wdtype = tuple(getattr(weight, "shape", ())), getattr(weight, "dtype", None)
+        if not isinstance(weight, (np.ndarray, DeviceArray)):
+            raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
+        cells = (-(-H // ch), -(-W // cw))
+        if wshape == (H, W) and wdtype == np.float32:
+            kind = L.MA_SMOOTH_WEIGHT_F32
+        elif wshape == (H, W) and wdtype == np.uint8:
+            kind = L.MA_SMOOTH_WEIGHT_U8
+        elif cell_size is not None and wshape == cells and wdtype == np.float32:
+            kind = L.MA_SMOOTH_WEIGHT_CELLS
+        elif cell_size is not None:
+            raise ValueError(f"a weight must be float32 or uint8 of shape {(H, W)}, or float32 of shape {cells} for cells "
+                             f"{(ch, cw)}, got {wdtype} {wshape}")
+        else:
+            raise ValueError(f"a per-pixel weight must be float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+    if prior is None:
+        if clip is not None:
+            raise ValueError("clip only has a meaning together with a prior")
+        return H, W, kind, ch, cw, None, 0.0
+    try:
+        t = np.array(prior, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("prior must be a 2 x 3 matrix") from None
+    if t.shape != (2, 3) or not np.all(np.isfinite(t)):
+        raise ValueError("prior must be a finite 2 x 3 matrix")
+    c = _real(clip, "clip")
+    if not c > 0:
+        raise ValueError(f"clip must be > 0, got {clip!r}")
+    return H, W, kind, ch, cw, np.ascontiguousarray(t).ravel(), c
+
+
+def flow_affine_apply_params(flow, mat):
+    """Checks of apply(flow, A) (include/microaligner_flowaffine.h) without touching a device: (H, W, A as 6 float64)."""
+    H, W = _check_flow(flow)
+    try:
+        a = np.array(mat, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("the matrix must be 2 x 3") from None
+    if a.shape != (2, 3) or not np.all(np.isfinite(a)):
+        raise ValueError("the matrix must be a finite 2 x 3 matrix")
+    return H, W, np.ascontiguousarray(a).ravel()
+
+
+# ---- what the calls above report -------------------------------------------------------------------------------------------
 class SmoothInfo(collections.namedtuple("SmoothInfo", "unsupported")):
     """smooth_flow(..., return_info=True): the number of pixels whose smoothed value had no support (S2 <= min_support)."""
 
@@ -1158,6 +1213,34 @@ class Context:
         counts = (C.c_longlong * 3)()
         self._run(self.lib.ma_flow_fold_mask, flow.ptr, H, W, margin, keep.ptr, counts if return_info else None)
         return (keep, FoldInfo(*(int(v) for v in counts))) if return_info else keep
+
+    def flow_affine_moments(self, flow, weight=None, cell_size=None, prior=None, clip=None):
+        """The 14 weighted sums and 4 counts from which an affine fit of a flow is solved, per cell of the cell_size grid
+        (None: one cell, the whole image), about the image's centre (include/microaligner_flowaffine.h).  Device arrays in
+        (weight: None, an (H, W) float32 or uint8 array, or with cell_size a (gy, gx) float32 map); prior / clip: a 2 x 3
+        matrix in the centred frame and the residual in px beyond which a pixel is left out.  -> (sums (gy, gx, 14)
+        float64, counts (gy, gx, 4) int64 of used, invalid, unweighted, trimmed).  Synchronises."""
+        H, W, kind, ch, cw, pr, clip = flow_affine_moments_params(flow, weight, cell_size, prior, clip)
+        gy, gx = self._cell_grid_shape(H, W, min(ch, H), min(cw, W))
+        sums = np.empty((gy, gx, L.MA_FLOW_AFFINE_SUMS), np.float64)
+        counts = np.empty((gy, gx, L.MA_FLOW_AFFINE_COUNTS), np.int64)
+        self._run(self.lib.ma_flow_affine_moments, flow.ptr, H, W, None if weight is None else weight.ptr, kind, ch, cw,
+                  None if pr is None else pr.ctypes.data_as(C.POINTER(C.c_double)), clip,
+                  sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(C.POINTER(C.c_longlong)))
+        return sums, counts
+
+    def flow_affine_apply(self, flow, mat, out=None):
+        """apply(flow, A)(p) = p - A (p - flow(p)) in float64, rounded to float32 (include/microaligner_flowaffine.h): the
+        flow relative to the 2 x 3 matrix A (split), or with A = inv([tmat; 0 0 1]) the total flow of a matrix and a flow
+        relative to it (join).  A device array in, a new device array out; `out` may name the array to write instead,
+        `flow` itself included."""
+        H, W, a = flow_affine_apply_params(flow, mat)
+        if out is None:
+            out = self.empty((H, W, 2), np.float32)
+        elif not isinstance(out, DeviceArray) or out.dtype != np.float32 or out.shape != (H, W, 2):
+            raise ValueError(f"out must be a float32 DeviceArray of shape {(H, W, 2)}")
+        self._run(self.lib.ma_flow_affine_apply, flow.ptr, H, W, a.ctypes.data_as(C.POINTER(C.c_double)), out.ptr)
+        return out
 
     def transform_points(self, points, flow, direction, tmat=None, image_shape=None, max_iter=50, tol=1e-4,
                          return_info=False):

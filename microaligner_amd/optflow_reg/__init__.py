@@ -1,3 +1,4 @@
+from .flow_affine import FlowAffineInfo, FlowAffineMaps, fit_flow_affine, join_flow, local_affine, split_flow
 from .flow_calc import TileFlowCalc, farneback
 from .flow_grid import FlowGrid, FlowGridError, compress_flow, flow_grid_error
 from .flow_invert import invert_flow, transform_points
