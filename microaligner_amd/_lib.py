@@ -214,6 +214,12 @@ FLOWAFFINE_SIGNATURES = {
     "ma_flow_affine_apply": (_i, [_vp, _vp, _i, _i, C.POINTER(_d), _vp]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_texture.h (texture support maps of an image)
+MA_TEXTURE_MAX_RADIUS, MA_TEXTURE_CLASSES = 128, 3
+TEXTURE_SIGNATURES = {
+    "ma_texture_maps": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_f), _i, _f, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_longlong)]),
+}
+
 _lib = None
 
 
@@ -230,7 +236,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + \
             list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()) + list(FLOWINVERT_SIGNATURES.items()) + \
             list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()) + list(FLOWSMOOTH_SIGNATURES.items()) + \
-            list(FLOWAFFINE_SIGNATURES.items()):
+            list(FLOWAFFINE_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -139,6 +139,17 @@ def _real(v, name):
     return float(v)
 
 
+def _check_taps(taps):
+    if not isinstance(taps, np.ndarray) or taps.dtype != np.float32 or taps.ndim != 1:
+        raise ValueError("taps must be a 1-D float32 numpy array t[0 .. r]")
+    r = taps.shape[0] - 1
+    if not 1 <= r <= L.MA_SMOOTH_MAX_RADIUS:
+        raise ValueError(f"r must be in [1, {L.MA_SMOOTH_MAX_RADIUS}], got {r}")
+    if not (np.all(np.isfinite(taps)) and np.all(taps >= 0) and taps[0] > 0):
+        raise ValueError("taps must be finite and not negative, the centre tap positive")
+    return np.ascontiguousarray(taps), int(r)
+
+
 def gaussian_taps(sigma, truncate=3.0):
     """The taps t[0 .. r] of smooth_flow(): r = max(1, ceil(truncate * sigma)), t_k = exp(-k^2 / (2 sigma^2)) in float64,
     divided by t_0 + 2 sum(t_k), then rounded to float32.  ValueError for a sigma or truncate that is not finite and
@@ -172,13 +183,7 @@ def smooth_flow_params(flow, taps, weight=None, cell_size=None, where="all", min
     weight: None; an (H, W) float32 or uint8 array (numpy or device); or, with cell_size, a (gy, gx) float32 map on that
     cell grid.  ValueError for anything the C entry would refuse."""
     H, W = _check_flow(flow)
-    if not isinstance(taps, np.ndarray) or taps.dtype != np.float32 or taps.ndim != 1:
-        raise ValueError("taps must be a 1-D float32 numpy array t[0 .. r]")
-    r = taps.shape[0] - 1
-    if not 1 <= r <= L.MA_SMOOTH_MAX_RADIUS:
-        raise ValueError(f"r must be in [1, {L.MA_SMOOTH_MAX_RADIUS}], got {r}")
-    if not (np.all(np.isfinite(taps)) and np.all(taps >= 0) and taps[0] > 0):
-        raise ValueError("taps must be finite and not negative, the centre tap positive")
+    taps, r = _check_taps(taps)
     if not isinstance(where, str) or where not in SMOOTH_MODES:
         raise ValueError(f"unknown mode {where!r}: expected one of {sorted(SMOOTH_MODES)}")
     ms = _real(min_support, "min_support")
@@ -206,7 +211,7 @@ def smooth_flow_params(flow, taps, weight=None, cell_size=None, where="all", min
             kind = L.MA_SMOOTH_WEIGHT_U8
         else:
             raise ValueError(f"a per-pixel weight must be float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
-    return H, W, np.ascontiguousarray(taps), int(r), kind, ch, cw, SMOOTH_MODES[where], float(ms)
+    return H, W, taps, r, kind, ch, cw, SMOOTH_MODES[where], float(ms)
 
 
 def fold_mask_params(flow, margin):
@@ -215,6 +220,44 @@ def fold_mask_params(flow, margin):
     if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or not 0 <= int(margin) <= L.MA_FOLD_MASK_MAX_MARGIN:
         raise ValueError(f"margin must be an integer in [0, {L.MA_FOLD_MASK_MAX_MARGIN}], got {margin!r}")
     return H, W, int(margin)
+
+
+# ---- texture support maps of an image (include/microaligner_texture.h) ----------------------------------------------------
+TEXTURE_PLANES = ("lam_min", "lam_max", "weight")
+
+
+def texture_maps_params(img, taps, floor=None, cell_size=None, want=("lam_min", "lam_max")):
+    """Checks and host-side arguments of the texture support maps (include/microaligner_texture.h) without touching a
+    device: (H, W, dtype code, taps as C-contiguous float32, r, floor as float32 or None, cell_h, cell_w or None twice,
+    want as a tuple).  img: an (H, W) uint8, uint16 or float32 array (numpy or device).  want: which of "lam_min", "lam_max"
+    and "weight" to make; the weight needs a floor, and so do the per-cell counts that cell_size asks for.  ValueError for
+    anything the C entry would refuse."""
+    if not isinstance(img, (np.ndarray, DeviceArray)):
+        raise ValueError(f"img must be a numpy array or a DeviceArray, got {type(img).__name__}")
+    if len(img.shape) != 2:
+        raise ValueError(f"expected a 2D grayscale image, got shape {tuple(img.shape)}")
+    dtype = _dt(img.dtype)
+    H, W = (int(v) for v in img.shape)
+    if not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
+        raise ValueError(f"image sides must be in [1, 2^24], got {(H, W)}")
+    taps, r = _check_taps(taps)
+    if isinstance(want, str) or not all(isinstance(n, str) and n in TEXTURE_PLANES for n in want) or \
+            len(set(want)) != len(tuple(want)):
+        raise ValueError(f"want must name distinct planes among {TEXTURE_PLANES}, got {want!r}")
+    want = tuple(want)
+    if floor is not None:
+        fl = _real(floor, "floor")
+        with np.errstate(over="ignore"):
+            fl = np.float32(fl)
+        if not (np.isfinite(fl) and fl > 0):
+            raise ValueError(f"floor must be finite and positive as float32, got {floor!r}")
+        floor = float(fl)
+    elif "weight" in want or cell_size is not None:
+        raise ValueError("the weight and the per-cell counts need a floor")
+    ch, cw = (None, None) if cell_size is None else _cell_size_hw(cell_size)
+    if not want and cell_size is None:
+        raise ValueError("no output was asked for")
+    return H, W, dtype, taps, r, floor, ch, cw, want
 
 
 # ---- affine part of a flow (include/microaligner_flowaffine.h) -------------------------------------------------------------
@@ -1213,6 +1256,26 @@ class Context:
         counts = (C.c_longlong * 3)()
         self._run(self.lib.ma_flow_fold_mask, flow.ptr, H, W, margin, keep.ptr, counts if return_info else None)
         return (keep, FoldInfo(*(int(v) for v in counts))) if return_info else keep
+
+    def texture_maps(self, img, taps, floor=None, cell_size=None, want=("lam_min", "lam_max")):
+        """The texture support maps of an (H, W) uint8, uint16 or float32 device image with the symmetric kernel taps
+        t[0 .. r] (include/microaligner_texture.h): the eigenvalues of its smoothed structure tensor, and with `floor` (in
+        squared grey levels) the weight lam_min / (lam_min + floor) and, with cell_size, the per-cell counts of textured,
+        edge and flat pixels.  -> a dict of the planes named in `want` ((H, W) float32 device arrays) and, with cell_size,
+        "counts": a (gy, gx, 3) int64 numpy array, at the cost of a synchronisation."""
+        H, W, dtype, taps, r, floor, ch, cw, want = texture_maps_params(img, taps, floor, cell_size, want)
+        out = {n: self.empty((H, W), np.float32) for n in want}
+        ptr = {n: (out[n].ptr if n in out else None) for n in TEXTURE_PLANES}
+        counts = None
+        if ch is not None:
+            gy, gx = self._cell_grid_shape(H, W, min(ch, H), min(cw, W))
+            counts = np.empty((gy, gx, L.MA_TEXTURE_CLASSES), np.int64)
+        self._run(self.lib.ma_texture_maps, img.ptr, dtype, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r,
+                  0.0 if floor is None else floor, ptr["lam_min"], ptr["lam_max"], ptr["weight"], ch or 0, cw or 0,
+                  None if counts is None else counts.ctypes.data_as(C.POINTER(C.c_longlong)))
+        if counts is not None:
+            out["counts"] = counts
+        return out
 
     def flow_affine_moments(self, flow, weight=None, cell_size=None, prior=None, clip=None):
         """The 14 weighted sums and 4 counts from which an affine fit of a flow is solved, per cell of the cell_size grid
