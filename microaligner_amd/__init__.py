@@ -7,7 +7,7 @@ mirrors `from microaligner import OptFlowRegistrator, Warper` (microaligner/__in
 Compute runs in hand-written HIP kernels for gfx950 behind a C-ABI (include/microaligner_hip.h);
 there is no CPU fallback.
 """
-from .feature_reg import FeatureRegistrator
+from .feature_reg import FeatureRegistrator, align_affine, DirectAffineInfo
 from .optflow_reg import OptFlowRegistrator, TileFlowCalc, Warper, farneback, compose_flows, merge_two_flows, \
     invert_flow, transform_points, FlowGrid, FlowGridError, compress_flow, flow_grid_error, smooth_flow, fold_mask, \
     repair_flow, fit_flow_affine, split_flow, join_flow, local_affine, FlowAffineInfo, FlowAffineMaps
@@ -20,5 +20,5 @@ __all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc",
            "transform_img_with_tmat", "max_project_and_normalize", "assess_registration", "flow_qc", "RegistrationQC", "FlowQC",
            "residual_shift", "ResidualShift", "ShiftMaps", "FlowGrid", "FlowGridError", "compress_flow", "flow_grid_error",
            "smooth_flow", "fold_mask", "repair_flow", "fit_flow_affine", "split_flow", "join_flow", "local_affine", "FlowAffineInfo",
-           "FlowAffineMaps", "texture_maps", "TextureMaps"]
+           "FlowAffineMaps", "texture_maps", "TextureMaps", "align_affine", "DirectAffineInfo"]
 __version__ = "0.1.0"

@@ -220,6 +220,15 @@ TEXTURE_SIGNATURES = {
     "ma_texture_maps": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_f), _i, _f, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_direct.h (moments of the intensity-based affine
+# alignment)
+MA_DIRECT_AFFINE_SUMS, MA_DIRECT_AFFINE_COUNTS = 31, 5
+DIRECT_SIGNATURES = {
+    "ma_direct_affine_moments": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(_d), _d, _d, _vp, _i, _d, C.POINTER(_d),
+                                      C.POINTER(C.c_longlong)]),
+    "ma_direct_mask_weight": (_i, [_vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -236,7 +245,8 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(QC_SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + \
             list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()) + list(FLOWINVERT_SIGNATURES.items()) + \
             list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()) + list(FLOWSMOOTH_SIGNATURES.items()) + \
-            list(FLOWAFFINE_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()):
+            list(FLOWAFFINE_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + \
+            list(DIRECT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -314,6 +314,55 @@ def flow_affine_apply_params(flow, mat):
     return H, W, np.ascontiguousarray(a).ravel()
 
 
+# ---- intensity-based affine alignment (include/microaligner_direct.h) ------------------------------------------------------
+def _check_image(img, name):
+    if not isinstance(img, (np.ndarray, DeviceArray)):
+        raise ValueError(f"{name} must be a numpy array or a DeviceArray, got {type(img).__name__}")
+    if len(img.shape) != 2:
+        raise ValueError(f"{name}: expected a 2D grayscale image, got shape {tuple(img.shape)}")
+    return _dt(img.dtype)
+
+
+def direct_affine_moments_params(ref, mov, M, gain=1.0, bias=0.0, weight=None, clip=None):
+    """Checks and host-side arguments of the alignment moments (include/microaligner_direct.h) without touching a device:
+    (H, W, ref dtype code, mov dtype code, M as 6 float64, gain, bias, weight kind, clip as the C entry reads it: 0.0 for
+    none).  ref, mov: (H, W) uint8, uint16 or float32 arrays (numpy or device) of one shape.  M: a finite 2 x 3 matrix from
+    reference pixels to moving-image pixels.  weight: None, or an (H, W) float32 map or uint8 mask; a per-cell map is
+    refused.  clip: None, or a number > 0.  ValueError for anything the C entry would refuse."""
+    rdt, mdt = _check_image(ref, "ref"), _check_image(mov, "mov")
+    H, W = (int(v) for v in ref.shape)
+    if tuple(mov.shape) != (H, W):
+        raise ValueError(f"ref and mov must have one shape, got {tuple(ref.shape)} and {tuple(mov.shape)}")
+    if not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
+        raise ValueError(f"image sides must be in [1, 2^24], got {(H, W)}")
+    try:
+        m = np.array(M, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("M must be a 2 x 3 matrix") from None
+    if m.shape != (2, 3) or not np.all(np.isfinite(m)):
+        raise ValueError("M must be a finite 2 x 3 matrix")
+    gain, bias = _real(gain, "gain"), _real(bias, "bias")
+    if not (np.isfinite(gain) and np.isfinite(bias)):
+        raise ValueError(f"gain and bias must be finite, got {gain!r}, {bias!r}")
+    kind = L.MA_SMOOTH_WEIGHT_NONE
+    if weight is not None:
+        wshape, wdtype = tuple(getattr(weight, "shape", ())), getattr(weight, "dtype", None)
+        if not isinstance(weight, (np.ndarray, DeviceArray)):
+            raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
+        if wshape == (H, W) and wdtype == np.float32:
+            kind = L.MA_SMOOTH_WEIGHT_F32
+        elif wshape == (H, W) and wdtype == np.uint8:
+            kind = L.MA_SMOOTH_WEIGHT_U8
+        else:
+            raise ValueError(f"the weight must be per pixel, float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+    c = 0.0
+    if clip is not None:
+        c = _real(clip, "clip")
+        if not c > 0:
+            raise ValueError(f"clip must be > 0, got {clip!r}")
+    return H, W, rdt, mdt, np.ascontiguousarray(m).ravel(), gain, bias, kind, c
+
+
 # ---- what the calls above report -------------------------------------------------------------------------------------------
 class SmoothInfo(collections.namedtuple("SmoothInfo", "unsupported")):
     """smooth_flow(..., return_info=True): the number of pixels whose smoothed value had no support (S2 <= min_support)."""
@@ -1303,6 +1352,30 @@ class Context:
         elif not isinstance(out, DeviceArray) or out.dtype != np.float32 or out.shape != (H, W, 2):
             raise ValueError(f"out must be a float32 DeviceArray of shape {(H, W, 2)}")
         self._run(self.lib.ma_flow_affine_apply, flow.ptr, H, W, a.ctypes.data_as(C.POINTER(C.c_double)), out.ptr)
+        return out
+
+    def direct_affine_moments(self, ref, mov, M, gain=1.0, bias=0.0, weight=None, clip=None):
+        """The 31 weighted sums and 5 counts of one Gauss-Newton pass of the intensity-based affine alignment
+        (include/microaligner_direct.h): the reference against gain * mov(M p) + bias, mov sampled bilinearly, about the
+        image's centre.  Device arrays in (ref, mov: (H, W) uint8, uint16 or float32; weight: None, an (H, W) float32 map
+        or uint8 mask); M: 2 x 3, reference pixels to moving-image pixels; clip: the residual in grey levels beyond which a
+        pixel is left out.  -> (sums (31,) float64, counts (5,) int64 of used, outside, invalid, unweighted, trimmed).
+        Synchronises."""
+        H, W, rdt, mdt, m, gain, bias, kind, clip = direct_affine_moments_params(ref, mov, M, gain, bias, weight, clip)
+        sums = np.empty((L.MA_DIRECT_AFFINE_SUMS,), np.float64)
+        counts = np.empty((L.MA_DIRECT_AFFINE_COUNTS,), np.int64)
+        self._run(self.lib.ma_direct_affine_moments, ref.ptr, rdt, mov.ptr, mdt, H, W, m.ctypes.data_as(C.POINTER(C.c_double)),
+                  gain, bias, None if weight is None else weight.ptr, kind, clip,
+                  sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(C.POINTER(C.c_longlong)))
+        return sums, counts
+
+    def mask_weight(self, mask):
+        """A uint8 device mask as the float32 map of the same weights, nonzero = 1.0 (include/microaligner_direct.h): what
+        the pyramid of a mask is built from.  Stream ordered."""
+        if not isinstance(mask, DeviceArray) or mask.dtype != np.uint8 or mask.size < 1:
+            raise ValueError("mask must be a non-empty uint8 DeviceArray")
+        out = self.empty(mask.shape, np.float32)
+        self._run(self.lib.ma_direct_mask_weight, mask.ptr, mask.size, out.ptr)
         return out
 
     def transform_points(self, points, flow, direction, tmat=None, image_shape=None, max_iter=50, tol=1e-4,

@@ -75,6 +75,16 @@ class RegParam:
                 raise TypeError("Field SaveFlowGridStride has wrong data type <class 'bool'>, expected an integer")
             _check_min_max("SaveFlowGridStride", 1, None, d)
             self.SaveFlowGridStride = d["SaveFlowGridStride"]
+        # addition, FeatureReg only: refine every cycle's feature matrix by align_affine with this model
+        self.DirectRefine = None
+        if "DirectRefine" in d:
+            if optflow:
+                raise ValueError("Field DirectRefine belongs to FeatureReg only")
+            _check_dtype("DirectRefine", str, d)
+            models = ["affine", "similarity", "rigid", "translation"]
+            if d["DirectRefine"] not in models:
+                raise ValueError(f"Field DirectRefine value is not one of: {models}")
+            self.DirectRefine = d["DirectRefine"]
         _check_min_max("NumberPyramidLevels", 0, 8, d)
         _check_min_max("NumberIterationsPerLevel", 1, None, d)
         _check_min_max("TileSize", 20, None, d)
@@ -348,6 +358,19 @@ def _load_cycles(cfg):
     return out
 
 
+def refine_feature_matrix(ref_img, mov_img, tmat, model, log=print):
+    """FeatureReg's DirectRefine: align_affine from the feature matrix; the matrix that comes back is the refined one where
+    it was accepted, else the feature matrix.  Logs how far the image corners moved."""
+    from . import align_affine
+    out, info = align_affine(ref_img, mov_img, model, tmat=tmat, return_info=True)
+    h, w = ref_img.shape
+    corners = np.array([[x, y, 1.0] for x in (0.0, w - 1.0) for y in (0.0, h - 1.0)])
+    moved = float(np.hypot(*(corners @ (np.asarray(out, np.float64) - np.asarray(tmat, np.float64)).T).T).max())
+    log(f"DirectRefine ({model}): accepted {info.accepted}, corners moved by up to {moved:.3f} px, "
+        f"{100 * info.used_share:.0f} % of the pixels used")
+    return out
+
+
 def run_feature_reg(cfg, cycles, log=print):
     """run_feature_reg / do_feature_reg / transform_and_save_freg_imgs (__main__.py:226-286,440-516): every cycle's
     max-projected reference channel against the reference cycle's -> one 2x3 matrix per cycle -> every page padded to the
@@ -375,6 +398,8 @@ def run_feature_reg(cfg, cycles, log=print):
             mov, _ = pad_to_shape(max_project_and_normalize(arr[channel_index(names, cfg.ref_channel, f"cycle {cyc}")]), target)
             freg.mov_img = mov
             tmats[cyc] = freg.register(reuse_ref_img=True)
+            if cfg.feature.DirectRefine is not None:
+                tmats[cyc] = refine_feature_matrix(ref_img, mov, tmats[cyc], cfg.feature.DirectRefine, log)
         res = np.empty(arr.shape[:2] + target, arr.dtype)
         for c in range(arr.shape[0]):
             for z in range(arr.shape[1]):
