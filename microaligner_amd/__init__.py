@@ -10,7 +10,8 @@ there is no CPU fallback.
 from .feature_reg import FeatureRegistrator, align_affine, DirectAffineInfo
 from .optflow_reg import OptFlowRegistrator, TileFlowCalc, Warper, farneback, compose_flows, merge_two_flows, \
     invert_flow, transform_points, FlowGrid, FlowGridError, compress_flow, flow_grid_error, smooth_flow, fold_mask, \
-    repair_flow, fit_flow_affine, split_flow, join_flow, local_affine, FlowAffineInfo, FlowAffineMaps
+    repair_flow, fit_flow_affine, split_flow, join_flow, local_affine, FlowAffineInfo, FlowAffineMaps, \
+    refine_flow, FlowRefineInfo
 from .shared_modules.registration_qc import FlowQC, RegistrationQC, assess_registration, flow_qc
 from .shared_modules.residual_shift import ResidualShift, ShiftMaps, residual_shift
 from .shared_modules.texture import TextureMaps, texture_maps
@@ -20,5 +21,5 @@ __all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc",
            "transform_img_with_tmat", "max_project_and_normalize", "assess_registration", "flow_qc", "RegistrationQC", "FlowQC",
            "residual_shift", "ResidualShift", "ShiftMaps", "FlowGrid", "FlowGridError", "compress_flow", "flow_grid_error",
            "smooth_flow", "fold_mask", "repair_flow", "fit_flow_affine", "split_flow", "join_flow", "local_affine", "FlowAffineInfo",
-           "FlowAffineMaps", "texture_maps", "TextureMaps", "align_affine", "DirectAffineInfo"]
+           "FlowAffineMaps", "texture_maps", "TextureMaps", "align_affine", "DirectAffineInfo", "refine_flow", "FlowRefineInfo"]
 __version__ = "0.1.0"

@@ -229,6 +229,14 @@ DIRECT_SIGNATURES = {
     "ma_direct_mask_weight": (_i, [_vp, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_flowrefine.h (a regularised Lucas-Kanade step of a
+# flow against the images)
+MA_REFINE_MAX_RADIUS, MA_REFINE_STATS = 128, 3
+FLOWREFINE_SIGNATURES = {
+    "ma_flow_refine_step": (_i, [_vp, _vp, _i, _vp, _i, _i, C.POINTER(_f), _i, _f, _vp, _i, _f, _vp, _vp,
+                                 C.POINTER(C.c_longlong)]),
+}
+
 _lib = None
 
 
@@ -246,7 +254,7 @@ def load():
             list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()) + list(FLOWINVERT_SIGNATURES.items()) + \
             list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()) + list(FLOWSMOOTH_SIGNATURES.items()) + \
             list(FLOWAFFINE_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + \
-            list(DIRECT_SIGNATURES.items()):
+            list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -363,6 +363,44 @@ def direct_affine_moments_params(ref, mov, M, gain=1.0, bias=0.0, weight=None, c
     return H, W, rdt, mdt, np.ascontiguousarray(m).ravel(), gain, bias, kind, c
 
 
+# ---- refining a flow against the images (include/microaligner_flowrefine.h) ------------------------------------------------
+def _positive_f32(v, name):
+    x = _real(v, name)
+    with np.errstate(over="ignore"):
+        x = np.float32(x)
+    if not (np.isfinite(x) and x > 0):
+        raise ValueError(f"{name} must be finite and positive as float32, got {v!r}")
+    return float(x)
+
+
+def flow_refine_step_params(ref, warped, flow, taps, floor, weight=None, max_step=1.0):
+    """Checks and host-side arguments of one refinement step (include/microaligner_flowrefine.h) without touching a device:
+    (H, W, ref dtype code, taps as C-contiguous float32, r, floor as float32, weight kind, max_step as float32).  ref: an
+    (H, W) uint8, uint16 or float32 array (numpy or device); warped: (H, W) float32; flow: (H, W, 2) float32; weight: None, or
+    an (H, W) float32 map or uint8 mask.  ValueError for anything the C entry would refuse."""
+    rdt = _check_image(ref, "ref")
+    H, W = _check_flow(flow)
+    if tuple(ref.shape) != (H, W):
+        raise ValueError(f"ref must have the flow's (H, W) = {(H, W)}, got {tuple(ref.shape)}")
+    if not isinstance(warped, (np.ndarray, DeviceArray)) or warped.dtype != np.float32 or tuple(warped.shape) != (H, W):
+        raise ValueError(f"warped must be float32 of shape {(H, W)}, got {getattr(warped, 'dtype', None)} "
+                         f"{tuple(getattr(warped, 'shape', ()))}")
+    taps, r = _check_taps(taps)
+    floor, max_step = _positive_f32(floor, "floor"), _positive_f32(max_step, "max_step")
+    kind = L.MA_SMOOTH_WEIGHT_NONE
+    if weight is not None:
+        wshape, wdtype = tuple(getattr(weight, "shape", ())), getattr(weight, "dtype", None)
+        if not isinstance(weight, (np.ndarray, DeviceArray)):
+            raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
+        if wshape == (H, W) and wdtype == np.float32:
+            kind = L.MA_SMOOTH_WEIGHT_F32
+        elif wshape == (H, W) and wdtype == np.uint8:
+            kind = L.MA_SMOOTH_WEIGHT_U8
+        else:
+            raise ValueError(f"the weight must be per pixel, float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+    return H, W, rdt, taps, r, floor, kind, max_step
+
+
 # ---- what the calls above report -------------------------------------------------------------------------------------------
 class SmoothInfo(collections.namedtuple("SmoothInfo", "unsupported")):
     """smooth_flow(..., return_info=True): the number of pixels whose smoothed value had no support (S2 <= min_support)."""
@@ -376,6 +414,16 @@ class FoldInfo(collections.namedtuple("FoldInfo", "folded invalid dropped")):
 class RepairInfo(collections.namedtuple("RepairInfo", "rounds converged")):
     """repair_flow(..., return_info=True): (folded, invalid, dropped, unsupported) of every smoothing round, and whether
     the loop ended on a flow with nothing folded and nothing invalid."""
+
+
+class RefineStepInfo(collections.namedtuple("RefineStepInfo", "step_max clamped invalid")):
+    """Context.flow_refine_step(..., return_info=True): the largest |component| of the step in px (after the clamp), the
+    pixels where the clamp changed a component, and the pixels whose system had no solution (their step is 0)."""
+
+
+class FlowRefineInfo(collections.namedtuple("FlowRefineInfo", "steps iterations converged")):
+    """refine_flow(..., return_info=True): the RefineStepInfo (step_max, clamped, invalid) of every step taken, their
+    number, and whether the loop ended on a step with step_max <= tol."""
 
 
 class InvertInfo(collections.namedtuple("InvertInfo", "not_converged residual")):
@@ -1325,6 +1373,28 @@ class Context:
         if counts is not None:
             out["counts"] = counts
         return out
+
+    def flow_refine_step(self, ref, warped, flow, taps, floor, weight=None, max_step=1.0, return_info=False, out=None):
+        """One regularised Lucas-Kanade step of `flow` (include/microaligner_flowrefine.h): the 2 x 2 system of the
+        structure tensor of `warped` -- the float32 moving image resampled by `flow` -- smoothed with the symmetric kernel
+        taps t[0 .. r], plus `floor` on its diagonal, against the smoothed products of the gradients and warped - ref; the
+        solution, each component clamped to +-max_step, is added to the flow.  Device arrays in (ref: (H, W) uint8, uint16
+        or float32; weight: None, an (H, W) float32 map or uint8 mask), a new device array out; `out` may name the array to
+        write instead, `flow` itself included.  With return_info a RefineStepInfo(step_max, clamped, invalid) beside it, at
+        the cost of a synchronisation."""
+        H, W, rdt, taps, r, floor, kind, max_step = flow_refine_step_params(ref, warped, flow, taps, floor, weight, max_step)
+        if out is None:
+            out = self.empty((H, W, 2), np.float32)
+        elif not isinstance(out, DeviceArray) or out.dtype != np.float32 or out.shape != (H, W, 2):
+            raise ValueError(f"out must be a float32 DeviceArray of shape {(H, W, 2)}")
+        stats = (C.c_longlong * L.MA_REFINE_STATS)()
+        self._run(self.lib.ma_flow_refine_step, ref.ptr, rdt, warped.ptr, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r,
+                  floor, None if weight is None else weight.ptr, kind, max_step, flow.ptr, out.ptr,
+                  stats if return_info else None)
+        if not return_info:
+            return out
+        step_max = float(np.array([stats[2]], np.uint32).view(np.float32)[0])
+        return out, RefineStepInfo(step_max, int(stats[1]), int(stats[0]))
 
     def flow_affine_moments(self, flow, weight=None, cell_size=None, prior=None, clip=None):
         """The 14 weighted sums and 4 counts from which an affine fit of a flow is solved, per cell of the cell_size grid

@@ -2,6 +2,7 @@ from .flow_affine import FlowAffineInfo, FlowAffineMaps, fit_flow_affine, join_f
 from .flow_calc import TileFlowCalc, farneback
 from .flow_grid import FlowGrid, FlowGridError, compress_flow, flow_grid_error
 from .flow_invert import invert_flow, transform_points
+from .flow_refine import FlowRefineInfo, refine_flow
 from .flow_smooth import fold_mask, repair_flow, smooth_flow
 from .optflow_registrator import OptFlowRegistrator, compose_flows, merge_two_flows
 from .warper import Warper
