@@ -237,6 +237,13 @@ FLOWREFINE_SIGNATURES = {
                                  C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_landmarks.h (thin-plate spline of landmark pairs)
+MA_LANDMARK_CHUNK, MA_LANDMARK_MAX = 1, 1 << 20
+LANDMARK_SIGNATURES = {
+    "ma_landmark_flow": (_i, [_vp, _vp, _i, C.POINTER(_d), _d, _d, _d, _i, _i, _i, _vp]),
+    "ma_landmark_points": (_i, [_vp, _vp, _i, C.POINTER(_d), _d, _d, _d, _vp, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -254,7 +261,8 @@ def load():
             list(COMPOSE_SIGNATURES.items()) + list(FLOWCOMPOSE_SIGNATURES.items()) + list(FLOWINVERT_SIGNATURES.items()) + \
             list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()) + list(FLOWSMOOTH_SIGNATURES.items()) + \
             list(FLOWAFFINE_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + \
-            list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()):
+            list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()) + \
+            list(LANDMARK_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -601,6 +601,47 @@ def affine_grid_params(img_shape, img_dtype, grid, tmat, interpolation="linear")
     return interp, np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0]), 0, 0
 
 
+# ---- thin-plate spline of landmark pairs (include/microaligner_landmarks.h) -----------------------------------------------
+def _check_spline(cw, a6, c, k):
+    if not isinstance(cw, np.ndarray) or cw.dtype != np.float64 or cw.ndim != 2 or cw.shape[1] != 4:
+        raise ValueError("cw must be an (n, 4) float64 numpy array of (u.x, u.y, w.x, w.y)")
+    if cw.shape[0] > L.MA_LANDMARK_MAX:
+        raise ValueError(f"at most {L.MA_LANDMARK_MAX} landmarks per call, got {cw.shape[0]}")
+    try:
+        a6 = np.asarray(a6, dtype=np.float64).ravel()
+        c = np.asarray(c, dtype=np.float64).ravel()
+        k = float(k)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"the affine part, the centre and the scale must be numbers: {e}") from None
+    if a6.shape != (6,) or c.shape != (2,):
+        raise ValueError(f"the affine part must hold 6 values and the centre 2, got {a6.size} and {c.size}")
+    if not (np.all(np.isfinite(cw)) and np.all(np.isfinite(a6)) and np.all(np.isfinite(c)) and np.isfinite(k)):
+        raise ValueError("the landmark records, the affine part, the centre and the scale must be finite")
+    return np.ascontiguousarray(cw), a6, float(c[0]), float(c[1]), k
+
+
+def landmark_flow_params(cw, a6, c, k, shape, stride=1):
+    """Checks and host-side arguments of the spline on a grid (include/microaligner_landmarks.h) without touching a device:
+    (cw as a C-contiguous (n, 4) float64 array, a6 as 6 float64, cx, cy, k, H, W, stride).  ValueError for anything the C
+    entry would refuse, and for non-finite records."""
+    spline = _check_spline(cw, a6, c, k)
+    H, W = _check_grid_shape(shape)
+    if H > 1 << 24 or W > 1 << 24:
+        raise ValueError(f"flow sides must be in [1, 2^24], got {(H, W)}")
+    return spline + (H, W, _check_stride(stride))
+
+
+def landmark_points_params(cw, a6, c, k, points):
+    """Checks and host-side arguments of the spline at points without touching a device: the spline as
+    landmark_flow_params gives it, and the points as a C-contiguous (N, 2) float64 array."""
+    spline = _check_spline(cw, a6, c, k)
+    if not isinstance(points, np.ndarray) or points.dtype != np.float64 or points.ndim != 2 or points.shape[1] != 2:
+        raise ValueError("points must be an (N, 2) float64 numpy array of (x, y)")
+    if points.shape[0] >= 1 << 31:
+        raise ValueError("at most 2^31 - 1 points per call")
+    return spline + (np.ascontiguousarray(points),)
+
+
 class _HostBuffer:
     """Owner of one page-locked host buffer; exposes it through __array_interface__ so that numpy arrays built on
     it keep it alive (base chain), and hands the memory back to the pool when it dies."""
@@ -1476,6 +1517,24 @@ class Context:
             return out
         return out, PointsInfo(self.download_raw(d_conv, (n,), np.uint8).astype(bool),
                                self.download_raw(d_in, (n,), np.uint8).astype(bool))
+
+    # thin-plate spline of landmark pairs (include/microaligner_landmarks.h) -------------------------------------------------
+    def landmark_flow(self, cw, a6, c, k, shape, stride=1):
+        """The flow of the spline (records cw, affine part a6, centre c, scale k: a LandmarkFit's) on the nodes of the grid of
+        an (H, W) flow at `stride`: a DeviceArray (g(H, stride), g(W, stride), 2) float32; stride 1 is the dense flow."""
+        cw, a6, cx, cy, k, H, W, stride = landmark_flow_params(cw, a6, c, k, shape, stride)
+        d_cw = self._upload_raw(cw)
+        out = self.empty((grid_nodes(H, stride), grid_nodes(W, stride), 2), np.float32)
+        self._run(self.lib.ma_landmark_flow, d_cw.ptr, cw.shape[0], (C.c_double * 6)(*a6), cx, cy, k, H, W, stride, out.ptr)
+        return out
+
+    def landmark_points(self, cw, a6, c, k, points):
+        """The spline's sampling map s at (N, 2) float64 points (x, y): numpy in, a new (N, 2) float64 array out."""
+        cw, a6, cx, cy, k, pts = landmark_points_params(cw, a6, c, k, points)
+        d_cw, d_pts = self._upload_raw(cw), self._upload_raw(pts)
+        self._run(self.lib.ma_landmark_points, d_cw.ptr, cw.shape[0], (C.c_double * 6)(*a6), cx, cy, k, d_pts.ptr,
+                  pts.shape[0], d_pts.ptr)
+        return self.download_raw(d_pts, (pts.shape[0], 2), np.float64)
 
     def pyr_down(self, img, minmax=False):
         h, w = img.shape

@@ -4,5 +4,6 @@ from .flow_grid import FlowGrid, FlowGridError, compress_flow, flow_grid_error
 from .flow_invert import invert_flow, transform_points
 from .flow_refine import FlowRefineInfo, refine_flow
 from .flow_smooth import fold_mask, repair_flow, smooth_flow
+from .landmarks import LandmarkFit, fit_landmarks, landmark_flow, landmark_points
 from .optflow_registrator import OptFlowRegistrator, compose_flows, merge_two_flows
 from .warper import Warper
