@@ -7,7 +7,7 @@ mirrors `from microaligner import OptFlowRegistrator, Warper` (microaligner/__in
 Compute runs in hand-written HIP kernels for gfx950 behind a C-ABI (include/microaligner_hip.h);
 there is no CPU fallback.
 """
-from .feature_reg import FeatureRegistrator, align_affine, DirectAffineInfo
+from .feature_reg import FeatureRegistrator, align_affine, DirectAffineInfo, align_translation, TranslationInfo
 from .optflow_reg import OptFlowRegistrator, TileFlowCalc, Warper, farneback, compose_flows, merge_two_flows, \
     invert_flow, transform_points, FlowGrid, FlowGridError, compress_flow, flow_grid_error, smooth_flow, fold_mask, \
     repair_flow, fit_flow_affine, split_flow, join_flow, local_affine, FlowAffineInfo, FlowAffineMaps, \
@@ -22,5 +22,5 @@ __all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc",
            "residual_shift", "ResidualShift", "ShiftMaps", "FlowGrid", "FlowGridError", "compress_flow", "flow_grid_error",
            "smooth_flow", "fold_mask", "repair_flow", "fit_flow_affine", "split_flow", "join_flow", "local_affine", "FlowAffineInfo",
            "FlowAffineMaps", "texture_maps", "TextureMaps", "align_affine", "DirectAffineInfo", "refine_flow", "FlowRefineInfo",
-           "LandmarkFit", "fit_landmarks", "landmark_flow", "landmark_points"]
+           "LandmarkFit", "fit_landmarks", "landmark_flow", "landmark_points", "align_translation", "TranslationInfo"]
 __version__ = "0.1.0"

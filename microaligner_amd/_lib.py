@@ -244,6 +244,22 @@ LANDMARK_SIGNATURES = {
     "ma_landmark_points": (_i, [_vp, _vp, _i, C.POINTER(_d), _d, _d, _d, _vp, _i, _vp]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_translation.h (global translation search)
+MA_TRANSLATION_MAX_SHIFTS, MA_TRANSLATION_MAX_PIXELS = 1 << 20, 1 << 32
+
+
+class TranslationResult(C.Structure):
+    """ma_translation_result"""
+    _fields_ = [("dx", _i), ("dy", _i), ("delta_x", _d), ("delta_y", _d), ("score", _d), ("second", _d),
+                ("n", C.c_longlong), ("at_limit", _i), ("valid", _i)]
+
+
+TRANSLATION_SIGNATURES = {
+    "ma_translation_moments": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_ulonglong)]),
+    "ma_translation_scores": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_ulonglong), C.POINTER(_d)]),
+    "ma_translation_search": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(TranslationResult), C.POINTER(_d)]),
+}
+
 _lib = None
 
 
@@ -262,7 +278,7 @@ def load():
             list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()) + list(FLOWSMOOTH_SIGNATURES.items()) + \
             list(FLOWAFFINE_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + \
             list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()) + \
-            list(LANDMARK_SIGNATURES.items()):
+            list(LANDMARK_SIGNATURES.items()) + list(TRANSLATION_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

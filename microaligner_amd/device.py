@@ -401,6 +401,39 @@ def flow_refine_step_params(ref, warped, flow, taps, floor, weight=None, max_ste
     return H, W, rdt, taps, r, floor, kind, max_step
 
 
+# ---- global translation search (include/microaligner_translation.h) --------------------------------------------------------
+def translation_params(ref, mov, window, exclude=0):
+    """Checks and host-side arguments of the translation search (include/microaligner_translation.h) without touching a
+    device: (h, w, dx0, dx1, dy0, dy1, exclude).  ref, mov: (h, w) uint8 labels (numpy or device) of one shape; window:
+    (dx0, dx1, dy0, dy1), both ends included, at most 2^20 shifts; exclude: an int >= 0.  ValueError for anything the C
+    entries would refuse."""
+    for img, name in ((ref, "ref"), (mov, "mov")):
+        _check_image(img, name)
+        if img.dtype != np.uint8:
+            raise ValueError(f"{name} must be uint8 labels, got {img.dtype}")
+    h, w = (int(v) for v in ref.shape)
+    if tuple(mov.shape) != (h, w):
+        raise ValueError(f"ref and mov must have one shape, got {tuple(ref.shape)} and {tuple(mov.shape)}")
+    if h < 1 or w < 1 or h * w > L.MA_TRANSLATION_MAX_PIXELS:
+        raise ValueError(f"an image must hold 1 .. 2^32 pixels, got {(h, w)}")
+    try:
+        win = [v for v in window]
+    except TypeError:
+        raise ValueError("window must be (dx0, dx1, dy0, dy1)") from None
+    if len(win) != 4 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in win):
+        raise ValueError(f"window must be four ints (dx0, dx1, dy0, dy1), got {window!r}")
+    dx0, dx1, dy0, dy1 = (int(v) for v in win)
+    if any(abs(v) >= 1 << 31 for v in (dx0, dx1, dy0, dy1)):
+        raise ValueError(f"window out of the int range: {window!r}")
+    if dx1 < dx0 or dy1 < dy0:
+        raise ValueError(f"empty window {window!r}")
+    if (dx1 - dx0 + 1) * (dy1 - dy0 + 1) > L.MA_TRANSLATION_MAX_SHIFTS:
+        raise ValueError(f"a window must hold at most 2^20 shifts, got {(dx1 - dx0 + 1) * (dy1 - dy0 + 1)}")
+    if isinstance(exclude, bool) or not isinstance(exclude, (int, np.integer)) or not 0 <= exclude < 1 << 31:
+        raise ValueError(f"exclude must be an int >= 0, got {exclude!r}")
+    return h, w, dx0, dx1, dy0, dy1, int(exclude)
+
+
 # ---- what the calls above report -------------------------------------------------------------------------------------------
 class SmoothInfo(collections.namedtuple("SmoothInfo", "unsupported")):
     """smooth_flow(..., return_info=True): the number of pixels whose smoothed value had no support (S2 <= min_support)."""
@@ -1704,6 +1737,29 @@ class Context:
             if m is not None:
                 m["at_limit"], m["valid"] = m["at_limit"].astype(bool), m["valid"].astype(bool)
         return m0, m1
+
+    # global translation search (include/microaligner_translation.h) ----------------------------------------------------
+    def translation_moments(self, ref, mov, window):
+        """The five integer moments of the u8 labels (ref, mov) at every shift of window = (dx0, dx1, dy0, dy1), each over
+        that shift's overlap -> (5, ny, nx) uint64 in the order S_ab, S_a, S_aa, S_b, S_bb, entry [dy - dy0, dx - dx0]."""
+        h, w, dx0, dx1, dy0, dy1, _ = translation_params(ref, mov, window)
+        mom = np.empty((5, dy1 - dy0 + 1, dx1 - dx0 + 1), np.uint64)
+        self._run(self.lib.ma_translation_moments, ref.ptr, mov.ptr, h, w, dx0, dx1, dy0, dy1,
+                  mom.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+        return mom
+
+    def translation_search(self, ref, mov, window, exclude=2, table=False):
+        """The ZNCC peak of the u8 labels (ref, mov) over window = (dx0, dx1, dy0, dy1) -> a dict of dx, dy (int), delta_x,
+        delta_y, score, second (float), n (int), at_limit, valid (bool) and table ((ny, nx) float64 of all scores, or None
+        without table=True)."""
+        h, w, dx0, dx1, dy0, dy1, exclude = translation_params(ref, mov, window, exclude)
+        res = L.TranslationResult()
+        tab = np.empty((dy1 - dy0 + 1, dx1 - dx0 + 1)) if table else None
+        self._run(self.lib.ma_translation_search, ref.ptr, mov.ptr, h, w, dx0, dx1, dy0, dy1, exclude, C.byref(res),
+                  tab.ctypes.data_as(C.POINTER(C.c_double)) if table else None)
+        return dict(dx=int(res.dx), dy=int(res.dy), delta_x=float(res.delta_x), delta_y=float(res.delta_y),
+                    score=float(res.score), second=float(res.second), n=int(res.n), at_limit=bool(res.at_limit),
+                    valid=bool(res.valid), table=tab)
 
     def max_project(self, stack):
         nz = stack.shape[0]

@@ -85,6 +85,13 @@ class RegParam:
             if d["DirectRefine"] not in models:
                 raise ValueError(f"Field DirectRefine value is not one of: {models}")
             self.DirectRefine = d["DirectRefine"]
+        # addition, FeatureReg only: where a cycle's feature matrix is the identity, take align_translation's if accepted
+        self.TranslationFallback = False
+        if "TranslationFallback" in d:
+            if optflow:
+                raise ValueError("Field TranslationFallback belongs to FeatureReg only")
+            _check_dtype("TranslationFallback", bool, d)
+            self.TranslationFallback = d["TranslationFallback"]
         _check_min_max("NumberPyramidLevels", 0, 8, d)
         _check_min_max("NumberIterationsPerLevel", 1, None, d)
         _check_min_max("TileSize", 20, None, d)
@@ -371,6 +378,19 @@ def refine_feature_matrix(ref_img, mov_img, tmat, model, log=print):
     return out
 
 
+def translation_fallback(ref_img, mov_img, tmat, log=print):
+    """FeatureReg's TranslationFallback: where the feature stage came back with exactly the identity (it found no matrix it
+    trusts), align_translation's matrix if that was accepted, else the identity as it is.  Logs what the search found."""
+    from .feature_reg import affine_math
+    if not np.array_equal(np.asarray(tmat, np.float64), affine_math.IDENTITY):
+        return tmat
+    from . import align_translation
+    out, info = align_translation(ref_img, mov_img, return_info=True)
+    log(f"TranslationFallback: shift ({info.shift[0]:.2f}, {info.shift[1]:.2f}) px, score {info.score:.4f}, "
+        f"distinct {info.distinct:.4f}, accepted {info.accepted}")
+    return out if info.accepted else tmat
+
+
 def run_feature_reg(cfg, cycles, log=print):
     """run_feature_reg / do_feature_reg / transform_and_save_freg_imgs (__main__.py:226-286,440-516): every cycle's
     max-projected reference channel against the reference cycle's -> one 2x3 matrix per cycle -> every page padded to the
@@ -398,6 +418,8 @@ def run_feature_reg(cfg, cycles, log=print):
             mov, _ = pad_to_shape(max_project_and_normalize(arr[channel_index(names, cfg.ref_channel, f"cycle {cyc}")]), target)
             freg.mov_img = mov
             tmats[cyc] = freg.register(reuse_ref_img=True)
+            if cfg.feature.TranslationFallback:
+                tmats[cyc] = translation_fallback(ref_img, mov, tmats[cyc], log)
             if cfg.feature.DirectRefine is not None:
                 tmats[cyc] = refine_feature_matrix(ref_img, mov, tmats[cyc], cfg.feature.DirectRefine, log)
         res = np.empty(arr.shape[:2] + target, arr.dtype)
