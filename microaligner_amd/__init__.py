@@ -15,6 +15,7 @@ from .optflow_reg import OptFlowRegistrator, TileFlowCalc, Warper, farneback, co
 from .shared_modules.registration_qc import FlowQC, RegistrationQC, assess_registration, flow_qc
 from .shared_modules.residual_shift import ResidualShift, ShiftMaps, residual_shift
 from .shared_modules.texture import TextureMaps, texture_maps
+from .shared_modules.normalize import NormalizeInfo, normalize_percentile
 from .shared_modules.utils import max_project_and_normalize, pad_to_shape, transform_img_with_tmat
 
 __all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc", "farneback", "merge_two_flows", "compose_flows", "invert_flow", "transform_points", "pad_to_shape",
@@ -22,5 +23,6 @@ __all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc",
            "residual_shift", "ResidualShift", "ShiftMaps", "FlowGrid", "FlowGridError", "compress_flow", "flow_grid_error",
            "smooth_flow", "fold_mask", "repair_flow", "fit_flow_affine", "split_flow", "join_flow", "local_affine", "FlowAffineInfo",
            "FlowAffineMaps", "texture_maps", "TextureMaps", "align_affine", "DirectAffineInfo", "refine_flow", "FlowRefineInfo",
-           "LandmarkFit", "fit_landmarks", "landmark_flow", "landmark_points", "align_translation", "TranslationInfo"]
+           "LandmarkFit", "fit_landmarks", "landmark_flow", "landmark_points", "align_translation", "TranslationInfo",
+           "normalize_percentile", "NormalizeInfo"]
 __version__ = "0.1.0"

@@ -260,6 +260,14 @@ TRANSLATION_SIGNATURES = {
     "ma_translation_search": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(TranslationResult), C.POINTER(_d)]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_quantile.h (order statistics of an image, scaling
+# to u8 between two given values)
+MA_Q_IGNORE_ZEROS, MA_Q_MAX_RANKS, MA_Q_MAX_PIXELS = 1, 8, 1 << 40
+QUANTILE_SIGNATURES = {
+    "ma_image_quantiles": (_i, [_vp, _vp, _i, _sz, _i, C.POINTER(_d), _i, C.POINTER(_d), C.POINTER(C.c_longlong)]),
+    "ma_normalize_range_u8": (_i, [_vp, _vp, _i, _sz, _d, _d, _vp]),
+}
+
 _lib = None
 
 
@@ -278,7 +286,8 @@ def load():
             list(RESIDUAL_SIGNATURES.items()) + list(FLOWGRID_SIGNATURES.items()) + list(FLOWSMOOTH_SIGNATURES.items()) + \
             list(FLOWAFFINE_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + \
             list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()) + \
-            list(LANDMARK_SIGNATURES.items()) + list(TRANSLATION_SIGNATURES.items()):
+            list(LANDMARK_SIGNATURES.items()) + list(TRANSLATION_SIGNATURES.items()) + \
+            list(QUANTILE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
            "flow_compose.hip", "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip", "texture.hip", "direct_affine.hip", "flow_refine.hip",
-           "landmarks.hip", "translation.hip"]
+           "landmarks.hip", "translation.hip", "quantile.hip"]
 HEADERS = [os.path.join(CSRC, "ma_internal.h"), os.path.join(CSRC, "remap_common.h"), os.path.join(CSRC, "nmi_score.h"),
            os.path.join(HERE, "..", "include", "microaligner_hip.h")]
 # headers of single sources that are off the measured path (not in HEADERS, so not in source_hash())
@@ -40,7 +40,8 @@ SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_q
                   "flow_refine.hip": [os.path.join(HERE, "..", "include", "microaligner_flowrefine.h"),
                                       os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h")],
                   "landmarks.hip": [os.path.join(HERE, "..", "include", "microaligner_landmarks.h")],
-                  "translation.hip": [os.path.join(HERE, "..", "include", "microaligner_translation.h")]}
+                  "translation.hip": [os.path.join(HERE, "..", "include", "microaligner_translation.h")],
+                  "quantile.hip": [os.path.join(HERE, "..", "include", "microaligner_quantile.h")]}
 # the grid-flow headers are also read by the two sources whose kernels take their flow from a grid: further dependencies of
 # those sources, beside the headers of their own above
 GRID_FLOW_USERS = {"warp_compose.hip": _FLOW_GRID, "flow_invert.hip": _FLOW_GRID}
@@ -100,12 +101,15 @@ def source_hash():
     #     reach;
     #   - the moments of the global translation search (ZNCC at every shift of a window over that shift's overlap), which
     #     only align_translation() reaches;
+    #   - the radix select of an image's order statistics and the scaling to u8 between two given values, which only
+    #     image_quantiles() / normalize_percentile() / a `percentiles` argument reach;
     #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps, and flow_jacobian.h, det J of
     #     the quality maps and the fold mask (SOURCE_HEADERS).
     off_path = {"probe.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "affine.hip", "qc.hip",
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
                 "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip",
-                "texture.hip", "direct_affine.hip", "flow_refine.hip", "landmarks.hip", "translation.hip"}
+                "texture.hip", "direct_affine.hip", "flow_refine.hip", "landmarks.hip", "translation.hip",
+                "quantile.hip"}
     for path in [os.path.join(CSRC, s) for s in SOURCES if s not in off_path] + HEADERS:
         h.update(open(path, "rb").read())
     h.update(" ".join(_flags()).encode())

@@ -434,6 +434,48 @@ def translation_params(ref, mov, window, exclude=0):
     return h, w, dx0, dx1, dy0, dy1, int(exclude)
 
 
+# ---- order statistics and range normalisation (include/microaligner_quantile.h) -------------------------------------------
+def image_quantiles_params(arr, q, ignore_zeros=False):
+    """Checks and host-side arguments of Context.image_quantiles (include/microaligner_quantile.h) without touching a
+    device: (dtype code, n, q as a float64 array, flags).  arr: a uint8 / uint16 / float32 array (numpy or device) of 1 ..
+    2^40 elements; q: one number or 1 .. 8 of them, each in [0, 1], in any order; ignore_zeros: a bool.  ValueError for
+    anything the C entry would refuse."""
+    if not hasattr(arr, "dtype") or not hasattr(arr, "shape") or np.dtype(arr.dtype) not in _DT:
+        raise ValueError(f"expected a uint8 / uint16 / float32 array, got {getattr(arr, 'dtype', type(arr))}")
+    n = 1
+    for v in arr.shape:
+        n *= int(v)
+    if not 1 <= n <= L.MA_Q_MAX_PIXELS:
+        raise ValueError(f"an image must hold 1 .. 2^40 pixels, got shape {tuple(arr.shape)}")
+    try:
+        qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError(f"q must be numbers in [0, 1], got {q!r}") from None
+    if qs.ndim != 1 or not 1 <= qs.size <= L.MA_Q_MAX_RANKS:
+        raise ValueError(f"q must hold 1 .. {L.MA_Q_MAX_RANKS} numbers, got {q!r}")
+    if not np.all((qs >= 0.0) & (qs <= 1.0)):              # false for a NaN
+        raise ValueError(f"every q must lie in [0, 1], got {q!r}")
+    if not isinstance(ignore_zeros, (bool, np.bool_)):
+        raise ValueError(f"ignore_zeros must be a bool, got {ignore_zeros!r}")
+    return _DT[np.dtype(arr.dtype)], n, np.ascontiguousarray(qs), L.MA_Q_IGNORE_ZEROS if ignore_zeros else 0
+
+
+def normalize_range_params(arr, lo, hi):
+    """Checks of Context.normalize_range_u8 without touching a device: (dtype code, n, lo, hi) with lo and hi finite
+    floats.  ValueError otherwise."""
+    if not hasattr(arr, "dtype") or not hasattr(arr, "shape") or np.dtype(arr.dtype) not in _DT:
+        raise ValueError(f"expected a uint8 / uint16 / float32 array, got {getattr(arr, 'dtype', type(arr))}")
+    n = 1
+    for v in arr.shape:
+        n *= int(v)
+    if n < 1:
+        raise ValueError(f"empty array of shape {tuple(arr.shape)}")
+    lo, hi = _real(lo, "lo"), _real(hi, "hi")
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"lo and hi must be finite, got {lo!r} and {hi!r}")
+    return _DT[np.dtype(arr.dtype)], n, lo, hi
+
+
 # ---- what the calls above report -------------------------------------------------------------------------------------------
 class SmoothInfo(collections.namedtuple("SmoothInfo", "unsupported")):
     """smooth_flow(..., return_info=True): the number of pixels whose smoothed value had no support (S2 <= min_support)."""
@@ -457,6 +499,11 @@ class RefineStepInfo(collections.namedtuple("RefineStepInfo", "step_max clamped 
 class FlowRefineInfo(collections.namedtuple("FlowRefineInfo", "steps iterations converged")):
     """refine_flow(..., return_info=True): the RefineStepInfo (step_max, clamped, invalid) of every step taken, their
     number, and whether the loop ended on a step with step_max <= tol."""
+
+
+class QuantileCounts(collections.namedtuple("QuantileCounts", "pop nonfinite zeros")):
+    """Context.image_quantiles: the pixels of the population, the NaN / +-Inf pixels left out of it, and the zeros left out
+    with ignore_zeros.  pop + nonfinite + zeros is the size of the image."""
 
 
 class InvertInfo(collections.namedtuple("InvertInfo", "not_converged residual")):
@@ -2013,6 +2060,26 @@ class Context:
     def normalize_minmax_u8(self, arr):
         out = self.empty(arr.shape, np.uint8)
         self._run(self.lib.ma_normalize_minmax_u8, arr.ptr, _dt(arr.dtype), arr.size, out.ptr)
+        return out
+
+    # order statistics and range normalisation (include/microaligner_quantile.h) ----------------------------------------
+    def image_quantiles(self, arr, q, ignore_zeros=False):
+        """The order statistics q (each in [0, 1], at most 8, numpy's method="lower") of a uint8 / uint16 / float32 device
+        array over its finite pixels -- without its zeros with ignore_zeros -> (values as a float64 array, NaN for an empty
+        population; QuantileCounts(pop, nonfinite, zeros))."""
+        dt, n, qs, flags = image_quantiles_params(arr, q, ignore_zeros)
+        values = np.empty(qs.size, np.float64)
+        counts = (C.c_longlong * 3)()
+        self._run(self.lib.ma_image_quantiles, arr.ptr, dt, n, flags, qs.ctypes.data_as(C.POINTER(C.c_double)), int(qs.size),
+                  values.ctypes.data_as(C.POINTER(C.c_double)), counts)
+        return values, QuantileCounts(int(counts[0]), int(counts[1]), int(counts[2]))
+
+    def normalize_range_u8(self, arr, lo, hi):
+        """arr scaled so that lo -> 0 and hi -> 255, clamped and rounded half to even -> a uint8 DeviceArray; all zeros for
+        hi <= lo.  Stream ordered."""
+        dt, n, lo, hi = normalize_range_params(arr, lo, hi)
+        out = self.empty(arr.shape, np.uint8)
+        self._run(self.lib.ma_normalize_range_u8, arr.ptr, dt, n, lo, hi, out.ptr)
         return out
 
 

@@ -673,11 +673,21 @@ def register_cycle_chain(cycles: Sequence, ref_channel_ids=None, params: Optiona
     warped* reference image (the chain of :418-424), and every channel x z page of the cycle is warped with that
     one flow (warp_and_save_pages, :288-302) -- flow resident in HBM, page transfers overlapped.
     Returns (aligned cycles as arrays of the input shape and dtype, flows as numpy arrays; flows[0] is None).
-    The chain is serial across cycles; run it on one rank (pages of a cycle can be sharded with warp_pages)."""
+    The chain is serial across cycles; run it on one rank (pages of a cycle can be sharded with warp_pages).
+    params: attributes of the OptFlowRegistrator, and two keys of the normalisation that are taken out before:
+    normalize_percentiles=(low, high) and normalize_ignore_zeros (max_project_and_normalize's percentiles and
+    ignore_zeros; absent, the reference's min-max scaling)."""
     import numpy as np
     from . import OptFlowRegistrator, Warper
     from .shared_modules.utils import max_project_and_normalize
     params = dict(params or {})
+    norm = {}
+    if params.get("normalize_percentiles") is not None:
+        norm = dict(percentiles=params["normalize_percentiles"], ignore_zeros=bool(params.get("normalize_ignore_zeros", False)))
+    elif params.get("normalize_ignore_zeros"):
+        raise ValueError("normalize_ignore_zeros belongs to normalize_percentiles=(low, high)")
+    params.pop("normalize_percentiles", None)
+    params.pop("normalize_ignore_zeros", None)
     ref_channel_ids = list(ref_channel_ids) if ref_channel_ids is not None else [0] * len(cycles)
     if len(ref_channel_ids) != len(cycles):
         raise ValueError("one reference channel id per cycle is required")
@@ -687,7 +697,7 @@ def register_cycle_chain(cycles: Sequence, ref_channel_ids=None, params: Optiona
         if stack.ndim != 4:
             raise ValueError(f"cycle {cyc}: expected a (C, Z, H, W) stack, got shape {stack.shape}")
         C_, Z_, H, W = stack.shape
-        mov_img = max_project_and_normalize(stack[ref_channel_ids[cyc]], on_device=True)
+        mov_img = max_project_and_normalize(stack[ref_channel_ids[cyc]], on_device=True, **norm)
         if cyc == 0:
             ref_img = mov_img                       # "Skipping as it is a reference image" (:411-413)
             aligned.append(stack.copy())

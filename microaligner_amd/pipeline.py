@@ -92,6 +92,24 @@ class RegParam:
                 raise ValueError("Field TranslationFallback belongs to FeatureReg only")
             _check_dtype("TranslationFallback", bool, d)
             self.TranslationFallback = d["TranslationFallback"]
+        # addition, both sections: scale every cycle's reference channel between two of its percentiles, [low, high] with
+        # 0 <= low < high <= 100, instead of between its minimum and its maximum (normalize_percentile) ...
+        self.NormalizePercentiles = None
+        if "NormalizePercentiles" in d:
+            _check_dtype("NormalizePercentiles", list, d)
+            pc = d["NormalizePercentiles"]
+            if len(pc) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in pc):
+                raise TypeError(f"Field NormalizePercentiles must be a list of two numbers [low, high], got {pc!r}")
+            if not (0 <= pc[0] < pc[1] <= 100):
+                raise ValueError(f"Field NormalizePercentiles must satisfy 0 <= low < high <= 100, got {pc!r}")
+            self.NormalizePercentiles = (float(pc[0]), float(pc[1]))
+        # ... and leave the exact zeros (padding, empty background) out of the percentiles
+        self.NormalizeIgnoreZeros = False
+        if "NormalizeIgnoreZeros" in d:
+            _check_dtype("NormalizeIgnoreZeros", bool, d)
+            if d["NormalizeIgnoreZeros"] and self.NormalizePercentiles is None:
+                raise ValueError("Field NormalizeIgnoreZeros needs NormalizePercentiles")
+            self.NormalizeIgnoreZeros = d["NormalizeIgnoreZeros"]
         _check_min_max("NumberPyramidLevels", 0, 8, d)
         _check_min_max("NumberIterationsPerLevel", 1, None, d)
         _check_min_max("TileSize", 20, None, d)
@@ -391,12 +409,32 @@ def translation_fallback(ref_img, mov_img, tmat, log=print):
     return out if info.accepted else tmat
 
 
+def project_reference_channel(reg_param, pages, what, log=print, **kw):
+    """max_project_and_normalize of a cycle's reference channel as the stage's section asks: min-max scaling, or between
+    NormalizePercentiles (without the zeros with NormalizeIgnoreZeros), logging the two values and the share of the pixels
+    the ranks leave outside them."""
+    from .shared_modules.utils import max_project_and_normalize
+    if reg_param.NormalizePercentiles is None:
+        return max_project_and_normalize(pages, **kw)
+    from .shared_modules.normalize import percentile_ranks
+    low, high = reg_param.NormalizePercentiles
+    img, info = max_project_and_normalize(pages, percentiles=(low, high), ignore_zeros=reg_param.NormalizeIgnoreZeros,
+                                          return_info=True, **kw)
+    if info.pop > 0:
+        rlo, rhi = percentile_ranks(low, high, info.pop)
+        n = info.pop + info.nonfinite + info.zeros
+        log(f"NormalizePercentiles {what}: lo {info.lo:.9g}, hi {info.hi:.9g}, at most {100.0 * (info.pop - 1 - rhi) / n:.3f} % "
+            f"of the pixels saturated above and {100.0 * rlo / n:.3f} % below" + (", degenerate (all zeros)" if info.degenerate else ""))
+    else:
+        log(f"NormalizePercentiles {what}: no pixel to take a percentile of (all zeros)")
+    return img
+
+
 def run_feature_reg(cfg, cycles, log=print):
     """run_feature_reg / do_feature_reg / transform_and_save_freg_imgs (__main__.py:226-286,440-516): every cycle's
     max-projected reference channel against the reference cycle's -> one 2x3 matrix per cycle -> every page padded to the
     common shape and transformed.  Returns the transformed cycles (in memory) and the matrices."""
     from . import FeatureRegistrator, pad_to_shape, transform_img_with_tmat
-    from .shared_modules.utils import max_project_and_normalize
     target = (max(a.shape[2] for _, a, _ in cycles), max(a.shape[3] for _, a, _ in cycles))
     freg = FeatureRegistrator()
     for k, v in cfg.feature.feature_kwargs().items():
@@ -405,8 +443,8 @@ def run_feature_reg(cfg, cycles, log=print):
     if cfg.ref_cycle not in by_id:
         raise ValueError(f"ReferenceCycle {cfg.ref_cycle} is not among the input cycles {sorted(by_id)}")
     ref_arr, ref_names = by_id[cfg.ref_cycle]
-    ref_img, _ = pad_to_shape(max_project_and_normalize(ref_arr[channel_index(ref_names, cfg.ref_channel, "the reference cycle")]),
-                              target)
+    ref_img, _ = pad_to_shape(project_reference_channel(
+        cfg.feature, ref_arr[channel_index(ref_names, cfg.ref_channel, "the reference cycle")], "reference cycle", log), target)
     freg.ref_img = ref_img
     tmats, out = {}, []
     for n, (cyc, arr, names) in enumerate(cycles):
@@ -415,7 +453,8 @@ def run_feature_reg(cfg, cycles, log=print):
             log("Skipping as it is a reference cycle")
             tmats[cyc] = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
         else:
-            mov, _ = pad_to_shape(max_project_and_normalize(arr[channel_index(names, cfg.ref_channel, f"cycle {cyc}")]), target)
+            mov, _ = pad_to_shape(project_reference_channel(
+                cfg.feature, arr[channel_index(names, cfg.ref_channel, f"cycle {cyc}")], f"cycle {cyc}", log), target)
             freg.mov_img = mov
             tmats[cyc] = freg.register(reuse_ref_img=True)
             if cfg.feature.TranslationFallback:
@@ -436,7 +475,6 @@ def run_optflow_reg(cfg, cycles, writer, log=print):
     With SaveFlowGridStride the flow of every registered cycle is also kept, as
     <OutputPrefix>optflow_reg_flowgrid_cycNNN.npz (FlowGrid.load reads it)."""
     from . import OptFlowRegistrator, Warper, compress_flow
-    from .shared_modules.utils import max_project_and_normalize
     reg = OptFlowRegistrator()
     for k, v in cfg.optflow.optflow_kwargs().items():
         setattr(reg, k, v)
@@ -446,7 +484,7 @@ def run_optflow_reg(cfg, cycles, writer, log=print):
     for n, (cyc, arr, names) in enumerate(cycles):
         log(f"Processing Cycle {cyc} [{n + 1}/{len(cycles)}]")
         ch = channel_index(names, cfg.ref_channel, f"cycle {cyc}")
-        mov_img = max_project_and_normalize(arr[ch], on_device=True)
+        mov_img = project_reference_channel(cfg.optflow, arr[ch], f"cycle {cyc}", log, on_device=True)
         dst = writer(n, cyc, arr)
         if n == 0:
             log("Skipping as it is a reference image")

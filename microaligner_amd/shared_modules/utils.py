@@ -41,11 +41,24 @@ def transform_img_with_tmat(img, target_shape: Tuple[int, int], transform_matrix
     return out.numpy().astype(original_dtype, copy=False)
 
 
-def max_project_and_normalize(pages, on_device: bool = False):
+def max_project_and_normalize(pages, on_device: bool = False, percentiles=None, ignore_zeros: bool = False,
+                              return_info: bool = False):
     """In-memory counterpart of read_and_max_project_pages (utils.py:75-95): element-wise maximum over the z pages
     (np.maximum fold, :92) followed by cv2.normalize(..., 0, 255, NORM_MINMAX, CV_8U) (:94), both on the device.
-    `pages`: a (Z, H, W) array or a sequence of (H, W) pages (uint8 / uint16 / float32).  Returns uint8."""
+    `pages`: a (Z, H, W) array or a sequence of (H, W) pages (uint8 / uint16 / float32).  Returns uint8.
+    percentiles=(low, high): the projection is scaled between these two of its percentiles instead of between its minimum
+    and its maximum (normalize_percentile, with ignore_zeros); return_info then adds its NormalizeInfo.  None, the default,
+    is the reference's min-max scaling."""
     from ..device import DeviceArray, get_context
+    if percentiles is not None:
+        from .normalize import percentile_params
+        try:
+            low, high = percentiles
+        except (TypeError, ValueError):
+            raise ValueError(f"percentiles must be (low, high), got {percentiles!r}") from None
+        percentile_params(low, high, ignore_zeros)                  # before any device work
+    elif ignore_zeros or return_info:
+        raise ValueError("ignore_zeros and return_info belong to percentiles=(low, high)")
     ctx = get_context()
     if isinstance(pages, DeviceArray):
         stack = pages
@@ -54,6 +67,12 @@ def max_project_and_normalize(pages, on_device: bool = False):
     if stack.ndim != 3:
         raise ValueError(f"expected (Z, H, W) pages, got shape {stack.shape}")
     proj = ctx.max_project(stack) if stack.shape[0] > 1 else DeviceArray(ctx, stack.shape[1:], stack.dtype, stack.ptr, 0, owner=False)
+    if percentiles is not None:
+        from .normalize import normalize_percentile
+        out, info = normalize_percentile(proj, low, high, ignore_zeros=ignore_zeros, on_device=True, return_info=True)
+        del proj
+        out = out if on_device else out.numpy()
+        return (out, info) if return_info else out
     out = ctx.normalize_minmax_u8(proj)
     del proj
     return out if on_device else out.numpy()
