@@ -24,6 +24,7 @@ _INTERP_HEADERS = [os.path.join(HERE, "..", "include", "microaligner_interp.h"),
 _CELL_GRID = os.path.join(CSRC, "cell_grid.h")
 _FLOW_GRID = [os.path.join(HERE, "..", "include", "microaligner_flowgrid.h"), os.path.join(CSRC, "flow_grid_eval.h")]
 _FLOW_JACOBIAN = os.path.join(CSRC, "flow_jacobian.h")   # det J, stated once for the quality maps and the fold mask
+_WINDOW_FIR = os.path.join(CSRC, "window_fir.h")   # the separable FIR tile of the smoothing, the texture maps and the refinement
 SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_qc.h"), _CELL_GRID, _FLOW_JACOBIAN],
                   "remap_interp.hip": _INTERP_HEADERS,
                   "warp_compose.hip": _INTERP_HEADERS + [os.path.join(HERE, "..", "include", "microaligner_compose.h")],
@@ -31,14 +32,15 @@ SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_q
                   "flow_invert.hip": [os.path.join(HERE, "..", "include", "microaligner_flowinvert.h")],
                   "residual_shift.hip": [os.path.join(HERE, "..", "include", "microaligner_residual.h"), _CELL_GRID],
                   "flow_grid.hip": _FLOW_GRID + [_CELL_GRID],
-                  "flow_smooth.hip": [os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID, _FLOW_JACOBIAN],
+                  "flow_smooth.hip": [os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID, _FLOW_JACOBIAN,
+                                      _WINDOW_FIR],
                   "flow_affine.hip": [os.path.join(HERE, "..", "include", "microaligner_flowaffine.h"),
                                       os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID],
-                  "texture.hip": [os.path.join(HERE, "..", "include", "microaligner_texture.h"), _CELL_GRID],
+                  "texture.hip": [os.path.join(HERE, "..", "include", "microaligner_texture.h"), _CELL_GRID, _WINDOW_FIR],
                   "direct_affine.hip": [os.path.join(HERE, "..", "include", "microaligner_direct.h"),
                                         os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h")],
                   "flow_refine.hip": [os.path.join(HERE, "..", "include", "microaligner_flowrefine.h"),
-                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h")],
+                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WINDOW_FIR],
                   "landmarks.hip": [os.path.join(HERE, "..", "include", "microaligner_landmarks.h")],
                   "translation.hip": [os.path.join(HERE, "..", "include", "microaligner_translation.h")],
                   "quantile.hip": [os.path.join(HERE, "..", "include", "microaligner_quantile.h")]}
@@ -103,8 +105,9 @@ def source_hash():
     #     only align_translation() reaches;
     #   - the radix select of an image's order statistics and the scaling to u8 between two given values, which only
     #     image_quantiles() / normalize_percentile() / a `percentiles` argument reach;
-    #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps, and flow_jacobian.h, det J of
-    #     the quality maps and the fold mask (SOURCE_HEADERS).
+    #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps, flow_jacobian.h, det J of
+    #     the quality maps and the fold mask, and window_fir.h, the separable FIR tile of the flow smoothing, the texture
+    #     maps and the flow refinement (SOURCE_HEADERS).
     off_path = {"probe.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "affine.hip", "qc.hip",
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
                 "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip",

@@ -1,23 +1,15 @@
 // Weighted Gaussian smoothing of a flow and the fold mask (include/microaligner_flowsmooth.h).  Off the measured path:
 // nothing in register() or warp() calls it.
 //
-// The smoothing is a separable FIR over the three planes w*u, w*v, w with up to 257 taps, in two launches through a
-// 12 B/px workspace that holds the row pass's planes TRANSPOSED ((W, H) each).  Both passes are then the same tile: 64
-// lines (lanes) x FS_S = FS_NW * FS_R outputs along the filtered axis, which is the fast axis of what the pass reads.
-//   - staging: a wave reads a line's span (outputs + r halo + guards) with consecutive lanes on consecutive elements
-//     (coalesced: float2 flow loads in the row pass, float loads of a transposed plane in the column pass) into
-//     LDS [64 lines][pitch], pitch odd, so that these writes and the filter's reads (lane = line) are free of bank conflicts;
-//   - filter: a thread slides a register window along its line for FS_R consecutive outputs (d_sym_fir_slide_pk, the
-//     window blurs' and DOG's filter), in the accumulation order of the header, one plane after the other through the same
-//     LDS tile;
-//   - output: lane = line, and a line of the input is a column of the output, so the stores are coalesced as well: the row
-//     pass writes its planes transposed, the column pass writes out (and reads flow / weight for the blend) row-major.
-// One kernel family for every r in 1 .. 128: LDS is sized by r at launch (43 KiB at r = 18, 97 KiB at r = 128).
-// Bound by the instructions it issues (two LDS reads and three packed operations per tap and 16 outputs), like the window
-// blurs, not by bytes; at large r the halo (2r staged elements beside 128 outputs per line) adds to it.
+// The smoothing is the separable window FIR of window_fir.h over the three planes w*u, w*v, w (a 12 B/px workspace).
+//   - The row pass stages the planes from the flow (float2 loads) and the weight, one plane after the other.
+//   - The column pass keeps the three filtered planes in registers and ends in the divide and the blend: it reads flow and
+//     weight again only for the blend, and counts the pixels without support, one integer atomic per wave.
+// LDS is sized by r at launch (43 KiB at r = 18, 97 KiB at r = 128).
 #include "../../include/microaligner_flowsmooth.h"
 #include "cell_grid.h"
 #include "flow_jacobian.h"
+#include "window_fir.h"
 
 #include <cmath>
 #include <vector>
@@ -25,14 +17,7 @@
 namespace {
 
 constexpr int FS_SIDE_MAX = 1 << 24;
-constexpr int FS_NW = 8, FS_R = 16, FS_S = FS_NW * FS_R;   // waves per block, outputs per thread, outputs per line and block
-constexpr int FS_G = 2;                                     // guard elements either side of the halo (d_sym_fir_slide_pk)
-constexpr int FS_TAPS = 8 + MA_SMOOTH_MAX_RADIUS + 8;       // floats of a tap table in the MA_TAP layout
-
-static inline int fs_span(int r) { return FS_S + 2 * r + 2 * FS_G; }
-static inline int fs_pitch(int r) { return fs_span(r) | 1; }
-
-struct FsTaps { float t[MA_SMOOTH_MAX_RADIUS + 1]; };
+static_assert(MA_SMOOTH_MAX_RADIUS == WF_MAX_RADIUS, "the tile of window_fir.h is sized for this radius");
 
 struct FsWeight {
     const void* p;
@@ -58,7 +43,7 @@ __device__ __forceinline__ float fs_effective(float wgt, float2 f)
 }
 
 // the header's rule on an axis of n ones at position x: the samples inside the image are 1, the others 0
-__device__ __forceinline__ float fs_rule_of_ones(const FsTaps& taps, int r, int x, int n)
+__device__ __forceinline__ float fs_rule_of_ones(const WfTaps& taps, int r, int x, int n)
 {
     float a = taps.t[0] * 1.f;
     for (int k = 1; k <= r; k++) {
@@ -68,38 +53,33 @@ __device__ __forceinline__ float fs_rule_of_ones(const FsTaps& taps, int r, int 
     return a;
 }
 
-// aux[0 .. FS_TAPS): the taps in the MA_TAP layout; with `ones`: aux[FS_TAPS + x] = rs(x), aux[FS_TAPS + W + y] = cs(y)
-__global__ __launch_bounds__(256) void fs_setup_kernel(FsTaps taps, int r, int W, int H, int ones, float* __restrict__ aux)
+// aux[0 .. WF_TAPS): the taps in the MA_TAP layout; with `ones`: aux[WF_TAPS + x] = rs(x), aux[WF_TAPS + W + y] = cs(y)
+__global__ __launch_bounds__(256) void fs_setup_kernel(WfTaps taps, int r, int W, int H, int ones, float* __restrict__ aux)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < FS_TAPS) {
-        float v = 0.f;
-        if (i == 0) v = taps.t[0];
-        else if (i >= 8 && i - 7 <= r) v = taps.t[i - 7];
-        aux[i] = v;
-    }
+    if (i < WF_TAPS) wf_layout_tap(taps, r, (int)i, aux);
     if (!ones) return;
-    if (i < W) aux[FS_TAPS + i] = fs_rule_of_ones(taps, r, (int)i, W);
-    else if (i < (long long)W + H) aux[FS_TAPS + i] = fs_rule_of_ones(taps, r, (int)(i - W), H);
+    if (i < W) aux[WF_TAPS + i] = fs_rule_of_ones(taps, r, (int)i, W);
+    else if (i < (long long)W + H) aux[WF_TAPS + i] = fs_rule_of_ones(taps, r, (int)(i - W), H);
 }
 
-// Row pass.  Block: rows [y0, y0 + 64) x output columns [x0, x0 + FS_S); lane = row.  ws: the three (W, H) planes.
+// Row pass.  Block: rows [y0, y0 + 64) x output columns [x0, x0 + WF_S); lane = row.  ws: the three (W, H) planes.
 template <int KIND>
-__global__ __launch_bounds__(64 * FS_NW) void fs_row_kernel(const float2* __restrict__ flow, int H, int W, FsWeight wt, int r,
+__global__ __launch_bounds__(64 * WF_NW) void fs_row_kernel(const float2* __restrict__ flow, int H, int W, FsWeight wt, int r,
                                                             const float* __restrict__ taps, int nbx, float* __restrict__ ws)
 {
     extern __shared__ float lds[];   // [64][pitch]
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int span = FS_S + 2 * r + 2 * FS_G, pitch = span | 1;
-    const int x0 = (int)(blockIdx.x % nbx) * FS_S, y0 = (int)(blockIdx.x / nbx) * 64;
+    const int span = WF_S + 2 * r + 2 * WF_G, pitch = span | 1;
+    const int x0 = (int)(blockIdx.x % nbx) * WF_S, y0 = (int)(blockIdx.x / nbx) * 64;
     const size_t plane = (size_t)H * W;
     for (int p = 0; p < 3; p++) {
-        for (int row = wv; row < 64; row += FS_NW) {
+        for (int row = wv; row < 64; row += WF_NW) {
             const int y = y0 + row;
             float* line = lds + row * pitch;
             for (int c = lane; c < span; c += 64) {
-                const int x = x0 - r - FS_G + c;
+                const int x = x0 - r - WF_G + c;
                 float val = 0.f;
                 if (y < H && x >= 0 && x < W) {
                     const size_t i = (size_t)y * W + x;
@@ -111,23 +91,23 @@ __global__ __launch_bounds__(64 * FS_NW) void fs_row_kernel(const float2* __rest
             }
         }
         __syncthreads();
-        float acc[FS_R];
-        d_sym_fir_slide_pk<FS_R, false, false>(lds + lane * pitch, FS_G + r + wv * FS_R, r, taps, acc);
+        float acc[WF_R];
+        d_sym_fir_slide_pk<WF_R, false, false>(lds + lane * pitch, WF_G + r + wv * WF_R, r, taps, acc);
         __syncthreads();
         const int y = y0 + lane;
         float* dst = ws + p * plane;
 #pragma unroll
-        for (int q = 0; q < FS_R; q++) {
-            const int x = x0 + wv * FS_R + q;
+        for (int q = 0; q < WF_R; q++) {
+            const int x = x0 + wv * WF_R + q;
             if (x < W && y < H) dst[(size_t)x * H + y] = acc[q];
         }
     }
 }
 
-// Column pass with the divide and the blend.  Block: columns [x0, x0 + 64) x output rows [y0, y0 + FS_S); lane = column.
+// Column pass with the divide and the blend.  Block: columns [x0, x0 + 64) x output rows [y0, y0 + WF_S); lane = column.
 // flow and out may be one array: neither is __restrict__, and a thread reads flow only at the pixel it writes.
 template <int KIND, int MODE>
-__global__ __launch_bounds__(64 * FS_NW) void fs_col_kernel(const float* __restrict__ ws, int H, int W, const float2* flow,
+__global__ __launch_bounds__(64 * WF_NW) void fs_col_kernel(const float* __restrict__ ws, int H, int W, const float2* flow,
                                                             FsWeight wt, int r, const float* __restrict__ aux, int nbx,
                                                             float min_support, float2* out,
                                                             unsigned long long* __restrict__ unsupported)
@@ -135,31 +115,31 @@ __global__ __launch_bounds__(64 * FS_NW) void fs_col_kernel(const float* __restr
     extern __shared__ float lds[];   // [64][pitch]
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int span = FS_S + 2 * r + 2 * FS_G, pitch = span | 1;
-    const int x0 = (int)(blockIdx.x % nbx) * 64, y0 = (int)(blockIdx.x / nbx) * FS_S;
+    const int span = WF_S + 2 * r + 2 * WF_G, pitch = span | 1;
+    const int x0 = (int)(blockIdx.x % nbx) * 64, y0 = (int)(blockIdx.x / nbx) * WF_S;
     const size_t plane = (size_t)H * W;
-    float S[3][FS_R];
+    float S[3][WF_R];
 #pragma unroll
     for (int p = 0; p < 3; p++) {
         const float* src = ws + p * plane;
-        for (int row = wv; row < 64; row += FS_NW) {
+        for (int row = wv; row < 64; row += WF_NW) {
             const int x = x0 + row;
             float* line = lds + row * pitch;
             for (int c = lane; c < span; c += 64) {
-                const int y = y0 - r - FS_G + c;
+                const int y = y0 - r - WF_G + c;
                 line[c] = (x < W && y >= 0 && y < H) ? src[(size_t)x * H + y] : 0.f;
             }
         }
         __syncthreads();
-        d_sym_fir_slide_pk<FS_R, false, false>(lds + lane * pitch, FS_G + r + wv * FS_R, r, aux, S[p]);
+        d_sym_fir_slide_pk<WF_R, false, false>(lds + lane * pitch, WF_G + r + wv * WF_R, r, aux, S[p]);
         __syncthreads();
     }
     const int x = x0 + lane;
     unsigned int missed = 0;
-    const float rs = (MODE == MA_SMOOTH_BLEND && x < W) ? aux[FS_TAPS + x] : 1.f;
+    const float rs = (MODE == MA_SMOOTH_BLEND && x < W) ? aux[WF_TAPS + x] : 1.f;
 #pragma unroll
-    for (int q = 0; q < FS_R; q++) {
-        const int y = y0 + wv * FS_R + q;
+    for (int q = 0; q < WF_R; q++) {
+        const int y = y0 + wv * WF_R + q;
         if (x >= W || y >= H) continue;
         const size_t i = (size_t)y * W + x;
         const float s2 = S[2][q];
@@ -170,7 +150,7 @@ __global__ __launch_bounds__(64 * FS_NW) void fs_col_kernel(const float* __restr
             const float2 f = flow[i];
             const float w = fs_effective(fs_weight_at<KIND>(wt, i, x, y), f);
             if (w > 0.f) {
-                const float sn = aux[FS_TAPS + W + y] * rs;
+                const float sn = aux[WF_TAPS + W + y] * rs;
                 const float c = __fdiv_rn(s2, sn);
                 const float d = 4.f * c - 2.f;
                 const float a = d > 0.f ? (d < 1.f ? d : 1.f) : 0.f;
@@ -254,59 +234,23 @@ __global__ __launch_bounds__(256) void fs_dilate_kernel(const unsigned char* __r
     if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(counts + 2, (unsigned long long)dropped);
 }
 
-// blocks of a 1-D grid over nbx x nby tiles
-static int fs_grid(long long nbx, long long nby, unsigned* blocks)
-{
-    MA_REQUIRE(nbx * nby <= 0x7fffffffLL, "flow too large");
-    *blocks = (unsigned)(nbx * nby);
-    return MA_OK;
-}
-
 template <int KIND>
 static int fs_launch(ma_ctx* ctx, const float* flow, int H, int W, const FsWeight& wt, int r, int mode, float min_support,
                      const float* aux, float* ws, float* out, unsigned long long* counter)
 {
-    const size_t lds = (size_t)64 * fs_pitch(r) * sizeof(float);
-    const int nbx1 = (W + FS_S - 1) / FS_S, nbx2 = (W + 63) / 64;
-    unsigned g1, g2;
-    MA_TRY(fs_grid(nbx1, (H + 63) / 64, &g1));
-    MA_TRY(fs_grid(nbx2, (H + FS_S - 1) / FS_S, &g2));
-    const void* row = reinterpret_cast<const void*>(fs_row_kernel<KIND>);
     const void* col = mode == MA_SMOOTH_BLEND ? reinterpret_cast<const void*>(fs_col_kernel<KIND, MA_SMOOTH_BLEND>)
                                               : reinterpret_cast<const void*>(fs_col_kernel<KIND, MA_SMOOTH_ALL>);
-    if (lds > 64 * 1024) {
-        MA_HIP(hipFuncSetAttribute(row, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MA_HIP(hipFuncSetAttribute(col, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    hipLaunchKernelGGL(fs_row_kernel<KIND>, dim3(g1), dim3(64 * FS_NW), lds, ctx->stream, (const float2*)flow, H, W, wt, r, aux,
-                       nbx1, ws);
+    WfShape s;
+    MA_TRY(wf_shape(H, W, r, "flow", reinterpret_cast<const void*>(fs_row_kernel<KIND>), col, &s));
+    hipLaunchKernelGGL(fs_row_kernel<KIND>, dim3(s.g_row), dim3(64 * WF_NW), s.lds, ctx->stream, (const float2*)flow, H, W, wt, r,
+                       aux, s.nbx_row, ws);
     if (mode == MA_SMOOTH_BLEND)
-        hipLaunchKernelGGL((fs_col_kernel<KIND, MA_SMOOTH_BLEND>), dim3(g2), dim3(64 * FS_NW), lds, ctx->stream, (const float*)ws,
-                           H, W, (const float2*)flow, wt, r, aux, nbx2, min_support, (float2*)out, counter);
+        hipLaunchKernelGGL((fs_col_kernel<KIND, MA_SMOOTH_BLEND>), dim3(s.g_col), dim3(64 * WF_NW), s.lds, ctx->stream,
+                           (const float*)ws, H, W, (const float2*)flow, wt, r, aux, s.nbx_col, min_support, (float2*)out, counter);
     else
-        hipLaunchKernelGGL((fs_col_kernel<KIND, MA_SMOOTH_ALL>), dim3(g2), dim3(64 * FS_NW), lds, ctx->stream, (const float*)ws,
-                           H, W, (const float2*)flow, wt, r, aux, nbx2, min_support, (float2*)out, counter);
+        hipLaunchKernelGGL((fs_col_kernel<KIND, MA_SMOOTH_ALL>), dim3(s.g_col), dim3(64 * WF_NW), s.lds, ctx->stream,
+                           (const float*)ws, H, W, (const float2*)flow, wt, r, aux, s.nbx_col, min_support, (float2*)out, counter);
     MA_HIP(hipGetLastError());
-    return MA_OK;
-}
-
-// the device counters of a call (n of them, zeroed) in the ctx workspace, if the caller asked for counts
-static int fs_counters(ma_ctx* ctx, bool wanted, int n, unsigned long long** counter)
-{
-    *counter = nullptr;
-    if (!wanted) return MA_OK;
-    MA_TRY(ma_ws_reserve(ctx, n * sizeof(unsigned long long)));
-    MA_TRY(ma_pinned_reserve(ctx, n * sizeof(unsigned long long)));
-    *counter = (unsigned long long*)ctx->ws;
-    MA_HIP(hipMemsetAsync(*counter, 0, n * sizeof(unsigned long long), ctx->stream));
-    return MA_OK;
-}
-
-static int fs_read_counters(ma_ctx* ctx, const unsigned long long* counter, int n, long long* host)
-{
-    MA_HIP(hipMemcpyAsync(ctx->pinned, counter, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    MA_HIP(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < n; k++) host[k] = (long long)((const unsigned long long*)ctx->pinned)[k];
     return MA_OK;
 }
 
@@ -325,17 +269,13 @@ extern "C" int ma_smooth_flow(ma_ctx* ctx, const float* flow, int H, int W, cons
     MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight != (const void*)out, "weight and out must be distinct arrays");
     MA_REQUIRE(weight_kind != MA_SMOOTH_WEIGHT_CELLS || (cell_h >= 1 && cell_w >= 1), "cell size must be >= 1");
     MA_REQUIRE(std::isfinite(min_support) && min_support >= 0.f, "min_support must be finite and not negative");
-    FsTaps taps{};
-    for (int k = 0; k <= r; k++) {
-        MA_REQUIRE(std::isfinite(taps_host[k]) && taps_host[k] >= 0.f, "taps must be finite and not negative");
-        taps.t[k] = taps_host[k];
-    }
-    MA_REQUIRE(taps.t[0] > 0.f, "the centre tap must be positive");
+    WfTaps taps;
+    MA_TRY(wf_taps(taps_host, r, &taps));
     MA_HIP(hipSetDevice(ctx->device));
     unsigned long long* counter;
-    MA_TRY(fs_counters(ctx, unsupported_host != nullptr, 1, &counter));
+    MA_TRY(wf_counters(ctx, unsupported_host != nullptr, 1, &counter));
     const int ones = mode == MA_SMOOTH_BLEND ? 1 : 0;
-    const size_t aux_n = (size_t)FS_TAPS + (ones ? (size_t)W + H : 0);
+    const size_t aux_n = (size_t)WF_TAPS + (ones ? (size_t)W + H : 0);
     float* aux = (float*)ma_pool_alloc(ctx, aux_n * sizeof(float));
     if (!aux) return MA_ENOMEM;
     float* ws = (float*)ma_pool_alloc(ctx, (size_t)H * W * 3 * sizeof(float));
@@ -357,7 +297,7 @@ extern "C" int ma_smooth_flow(ma_ctx* ctx, const float* flow, int H, int W, cons
     ma_pool_free(ctx, ws);
     ma_pool_free(ctx, aux);
     MA_TRY(rc);
-    if (unsupported_host) MA_TRY(fs_read_counters(ctx, counter, 1, unsupported_host));
+    if (unsupported_host) MA_TRY(wf_read_counters(ctx, counter, 1, unsupported_host));
     return MA_OK;
 }
 
@@ -369,12 +309,12 @@ extern "C" int ma_flow_fold_mask(ma_ctx* ctx, const float* flow, int H, int W, i
     MA_REQUIRE(margin >= 0 && margin <= MA_FOLD_MASK_MAX_MARGIN, "margin must be in [0, 32]");
     const int nbx1 = (W + 255) / 256, nbx2 = (W + FM_TW - 1) / FM_TW;
     unsigned g1, g2;
-    MA_TRY(fs_grid(nbx1, H, &g1));
-    MA_TRY(fs_grid(nbx2, (H + FM_TH - 1) / FM_TH, &g2));
+    MA_TRY(wf_grid(nbx1, H, "flow", &g1));
+    MA_TRY(wf_grid(nbx2, (H + FM_TH - 1) / FM_TH, "flow", &g2));
     MA_HIP(hipSetDevice(ctx->device));
     // the counters are always kept on the device (the kernels add to them); read back only on request
     unsigned long long* counter;
-    MA_TRY(fs_counters(ctx, true, 3, &counter));
+    MA_TRY(wf_counters(ctx, true, 3, &counter));
     unsigned char* bad = (unsigned char*)ma_pool_alloc(ctx, (size_t)H * W);
     if (!bad) return MA_ENOMEM;
     hipLaunchKernelGGL(fs_bad_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const float2*)flow, H, W, nbx1, bad, counter);
@@ -382,6 +322,6 @@ extern "C" int ma_flow_fold_mask(ma_ctx* ctx, const float* flow, int H, int W, i
                        counter);
     ma_pool_free(ctx, bad);
     MA_HIP(hipGetLastError());
-    if (counts_host) MA_TRY(fs_read_counters(ctx, counter, 3, counts_host));
+    if (counts_host) MA_TRY(wf_read_counters(ctx, counter, 3, counts_host));
     return MA_OK;
 }

@@ -2,10 +2,7 @@
 // one and per-cell class counts (include/microaligner_texture.h).  Off the measured path: nothing in register() or warp()
 // calls it.
 //
-// The smoothing is the separable FIR of the flow smoothing (flow_smooth.hip) over the three planes gx*gx, gx*gy, gy*gy with
-// up to 257 taps, in two launches through a 12 B/px workspace that holds the row pass's planes TRANSPOSED ((W, H) each), and
-// with the same tile: 64 lines (lanes) x TX_S = TX_NW * TX_R outputs along the filtered axis, coalesced staging into
-// LDS [64 lines][pitch], pitch odd, and d_sym_fir_slide_pk per thread in the accumulation order of the header.
+// The smoothing is the separable window FIR of window_fir.h over the three planes gx*gx, gx*gy, gy*gy (a 12 B/px workspace).
 //   - The row pass stages the products straight from the image, one plane after the other through the same LDS tile: every
 //     staged element reads I at its two neighbours along x, along y, or both, each read clamped into the image (the caches
 //     serve the re-reads; gx and gy are formed again for the plane that needs both).
@@ -14,20 +11,14 @@
 // LDS is sized by r at launch (58 KiB at r = 49, 97 KiB at r = 128).
 #include "../../include/microaligner_texture.h"
 #include "cell_grid.h"
+#include "window_fir.h"
 
 #include <cmath>
 
 namespace {
 
 constexpr int TX_SIDE_MAX = 1 << 24;
-constexpr int TX_NW = 8, TX_R = 16, TX_S = TX_NW * TX_R;   // waves per block, outputs per thread, outputs per line and block
-constexpr int TX_G = 2;                                     // guard elements either side of the halo (d_sym_fir_slide_pk)
-constexpr int TX_TAPS = 8 + MA_TEXTURE_MAX_RADIUS + 8;      // floats of a tap table in the MA_TAP layout
-
-static inline int tx_span(int r) { return TX_S + 2 * r + 2 * TX_G; }
-static inline int tx_pitch(int r) { return tx_span(r) | 1; }
-
-struct TxTaps { float t[MA_TEXTURE_MAX_RADIUS + 1]; };
+static_assert(MA_TEXTURE_MAX_RADIUS == WF_MAX_RADIUS, "the tile of window_fir.h is sized for this radius");
 
 // which outputs the column pass makes; floor is read for weight and counts, the grid for counts
 struct TxOut {
@@ -38,18 +29,6 @@ struct TxOut {
     float floor;
     int ch, cw, gx;
 };
-
-// aux[0 .. TX_TAPS): the taps in the MA_TAP layout
-__global__ __launch_bounds__(256) void tx_setup_kernel(TxTaps taps, int r, float* __restrict__ aux)
-{
-    const int i = threadIdx.x;
-    if (i < TX_TAPS) {
-        float v = 0.f;
-        if (i == 0) v = taps.t[0];
-        else if (i >= 8 && i - 7 <= r) v = taps.t[i - 7];
-        aux[i] = v;
-    }
-}
 
 // plane P of the header at (x, y), which must lie inside the image: every read is clamped into it
 template <int P, typename T>
@@ -62,78 +41,52 @@ __device__ __forceinline__ float tx_product(const T* __restrict__ img, int H, in
     return P == 0 ? gx * gx : (P == 1 ? gx * gy : gy * gy);
 }
 
-// one plane of the row pass through the block's LDS tile
-template <int P, typename T>
-__device__ __forceinline__ void tx_row_plane(const T* __restrict__ img, int H, int W, int r, const float* __restrict__ taps,
-                                             int x0, int y0, int lane, int wv, float* lds, float* __restrict__ dst)
-{
-    const int span = TX_S + 2 * r + 2 * TX_G, pitch = span | 1;
-    for (int row = wv; row < 64; row += TX_NW) {
-        const int y = y0 + row;
-        float* line = lds + row * pitch;
-        for (int c = lane; c < span; c += 64) {
-            const int x = x0 - r - TX_G + c;
-            line[c] = (y < H && x >= 0 && x < W) ? tx_product<P>(img, H, W, x, y) : 0.f;
-        }
-    }
-    __syncthreads();
-    float acc[TX_R];
-    d_sym_fir_slide_pk<TX_R, false, false>(lds + lane * pitch, TX_G + r + wv * TX_R, r, taps, acc);
-    __syncthreads();
-    const int y = y0 + lane;
-#pragma unroll
-    for (int q = 0; q < TX_R; q++) {
-        const int x = x0 + wv * TX_R + q;
-        if (x < W && y < H) dst[(size_t)x * H + y] = acc[q];
-    }
-}
-
-// Row pass.  Block: rows [y0, y0 + 64) x output columns [x0, x0 + TX_S); lane = row.  ws: the three (W, H) planes.
+// Row pass.  ws: the three (W, H) planes.
 template <typename T>
-__global__ __launch_bounds__(64 * TX_NW) void tx_row_kernel(const T* __restrict__ img, int H, int W, int r,
+__global__ __launch_bounds__(64 * WF_NW) void tx_row_kernel(const T* __restrict__ img, int H, int W, int r,
                                                             const float* __restrict__ taps, int nbx, float* __restrict__ ws)
 {
     extern __shared__ float lds[];   // [64][pitch]
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int x0 = (int)(blockIdx.x % nbx) * TX_S, y0 = (int)(blockIdx.x / nbx) * 64;
+    const int x0 = (int)(blockIdx.x % nbx) * WF_S, y0 = (int)(blockIdx.x / nbx) * 64;
     const size_t plane = (size_t)H * W;
-    tx_row_plane<0>(img, H, W, r, taps, x0, y0, lane, wv, lds, ws);
-    tx_row_plane<1>(img, H, W, r, taps, x0, y0, lane, wv, lds, ws + plane);
-    tx_row_plane<2>(img, H, W, r, taps, x0, y0, lane, wv, lds, ws + 2 * plane);
+    wf_row_plane([=](int H, int W, int x, int y) { return tx_product<0>(img, H, W, x, y); }, H, W, r, taps, x0, y0, lane, wv, lds, ws);
+    wf_row_plane([=](int H, int W, int x, int y) { return tx_product<1>(img, H, W, x, y); }, H, W, r, taps, x0, y0, lane, wv, lds, ws + plane);
+    wf_row_plane([=](int H, int W, int x, int y) { return tx_product<2>(img, H, W, x, y); }, H, W, r, taps, x0, y0, lane, wv, lds, ws + 2 * plane);
 }
 
 // Column pass with the eigenvalues, the weight and the class counts.  Block: columns [x0, x0 + 64) x output rows
-// [y0, y0 + TX_S); lane = column, a wave holds TX_R rows of 64 columns.
-__global__ __launch_bounds__(64 * TX_NW) void tx_col_kernel(const float* __restrict__ ws, int H, int W, int r,
+// [y0, y0 + WF_S); lane = column, a wave holds WF_R rows of 64 columns.
+__global__ __launch_bounds__(64 * WF_NW) void tx_col_kernel(const float* __restrict__ ws, int H, int W, int r,
                                                             const float* __restrict__ taps, int nbx, TxOut o)
 {
     extern __shared__ float lds[];   // [64][pitch]
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int span = TX_S + 2 * r + 2 * TX_G, pitch = span | 1;
-    const int x0 = (int)(blockIdx.x % nbx) * 64, y0 = (int)(blockIdx.x / nbx) * TX_S;
+    const int span = WF_S + 2 * r + 2 * WF_G, pitch = span | 1;
+    const int x0 = (int)(blockIdx.x % nbx) * 64, y0 = (int)(blockIdx.x / nbx) * WF_S;
     const size_t plane = (size_t)H * W;
-    float S[3][TX_R];
+    float S[3][WF_R];
 #pragma unroll
     for (int p = 0; p < 3; p++) {
         const float* src = ws + p * plane;
-        for (int row = wv; row < 64; row += TX_NW) {
+        for (int row = wv; row < 64; row += WF_NW) {
             const int x = x0 + row;
             float* line = lds + row * pitch;
             for (int c = lane; c < span; c += 64) {
-                const int y = y0 - r - TX_G + c;
+                const int y = y0 - r - WF_G + c;
                 line[c] = (x < W && y >= 0 && y < H) ? src[(size_t)x * H + y] : 0.f;
             }
         }
         __syncthreads();
-        d_sym_fir_slide_pk<TX_R, false, false>(lds + lane * pitch, TX_G + r + wv * TX_R, r, taps, S[p]);
+        d_sym_fir_slide_pk<WF_R, false, false>(lds + lane * pitch, WF_G + r + wv * WF_R, r, taps, S[p]);
         __syncthreads();
     }
-    const int x = x0 + lane, yb = y0 + wv * TX_R;
+    const int x = x0 + lane, yb = y0 + wv * WF_R;
     unsigned cls = 0xffffffffu;   // two bits per row of the wave: 0 textured, 1 edge, 2 flat, 3 outside the image
 #pragma unroll
-    for (int q = 0; q < TX_R; q++) {
+    for (int q = 0; q < WF_R; q++) {
         const int y = yb + q;
         if (x >= W || y >= H) continue;
         const size_t i = (size_t)y * W + x;
@@ -171,7 +124,7 @@ __global__ __launch_bounds__(64 * TX_NW) void tx_col_kernel(const float* __restr
             n0 = n1 = n2 = 0;
         };
 #pragma unroll
-        for (int q = 0; q < TX_R; q++) {
+        for (int q = 0; q < WF_R; q++) {
             const int y = yb + q;
             if (y < H) {             // wave-uniform
                 if (y == ynext) {
@@ -190,30 +143,16 @@ __global__ __launch_bounds__(64 * TX_NW) void tx_col_kernel(const float* __restr
     }
 }
 
-// blocks of a 1-D grid over nbx x nby tiles
-static int tx_grid(long long nbx, long long nby, unsigned* blocks)
-{
-    MA_REQUIRE(nbx * nby <= 0x7fffffffLL, "image too large");
-    *blocks = (unsigned)(nbx * nby);
-    return MA_OK;
-}
-
 template <typename T>
 static int tx_launch(ma_ctx* ctx, const void* img, int H, int W, int r, const float* aux, float* ws, const TxOut& o)
 {
-    const size_t lds = (size_t)64 * tx_pitch(r) * sizeof(float);
-    const int nbx1 = (W + TX_S - 1) / TX_S, nbx2 = (W + 63) / 64;
-    unsigned g1, g2;
-    MA_TRY(tx_grid(nbx1, (H + 63) / 64, &g1));
-    MA_TRY(tx_grid(nbx2, (H + TX_S - 1) / TX_S, &g2));
-    if (lds > 64 * 1024) {
-        MA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tx_row_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-        MA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tx_col_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-    }
-    hipLaunchKernelGGL(tx_row_kernel<T>, dim3(g1), dim3(64 * TX_NW), lds, ctx->stream, (const T*)img, H, W, r, aux, nbx1, ws);
-    hipLaunchKernelGGL(tx_col_kernel, dim3(g2), dim3(64 * TX_NW), lds, ctx->stream, (const float*)ws, H, W, r, aux, nbx2, o);
+    WfShape s;
+    MA_TRY(wf_shape(H, W, r, "image", reinterpret_cast<const void*>(tx_row_kernel<T>),
+                    reinterpret_cast<const void*>(tx_col_kernel), &s));
+    hipLaunchKernelGGL(tx_row_kernel<T>, dim3(s.g_row), dim3(64 * WF_NW), s.lds, ctx->stream, (const T*)img, H, W, r, aux,
+                       s.nbx_row, ws);
+    hipLaunchKernelGGL(tx_col_kernel, dim3(s.g_col), dim3(64 * WF_NW), s.lds, ctx->stream, (const float*)ws, H, W, r, aux,
+                       s.nbx_col, o);
     MA_HIP(hipGetLastError());
     return MA_OK;
 }
@@ -228,12 +167,8 @@ extern "C" int ma_texture_maps(ma_ctx* ctx, const void* img, int dtype, int H, i
     MA_REQUIRE(H >= 1 && W >= 1 && H <= TX_SIDE_MAX && W <= TX_SIDE_MAX, "image sides must be in [1, 2^24]");
     MA_REQUIRE(r >= 1 && r <= MA_TEXTURE_MAX_RADIUS, "r must be in [1, 128]");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "unknown dtype");
-    TxTaps taps{};
-    for (int k = 0; k <= r; k++) {
-        MA_REQUIRE(std::isfinite(taps_host[k]) && taps_host[k] >= 0.f, "taps must be finite and not negative");
-        taps.t[k] = taps_host[k];
-    }
-    MA_REQUIRE(taps.t[0] > 0.f, "the centre tap must be positive");
+    WfTaps taps;
+    MA_TRY(wf_taps(taps_host, r, &taps));
     TxOut o{lam_min, lam_max, weight, nullptr, INFINITY, 1, 1, 1};
     if (weight || counts_host) {
         MA_REQUIRE(std::isfinite(floor) && floor > 0.f, "floor must be finite and positive");
@@ -249,7 +184,7 @@ extern "C" int ma_texture_maps(ma_ctx* ctx, const void* img, int dtype, int H, i
     }
     MA_HIP(hipSetDevice(ctx->device));
     const size_t counts_bytes = (size_t)ncells * MA_TEXTURE_CLASSES * sizeof(unsigned long long);
-    float* aux = (float*)ma_pool_alloc(ctx, TX_TAPS * sizeof(float));
+    float* aux = (float*)ma_pool_alloc(ctx, WF_TAPS * sizeof(float));
     if (!aux) return MA_ENOMEM;
     float* ws = (float*)ma_pool_alloc(ctx, (size_t)H * W * 3 * sizeof(float));
     if (!ws) {
@@ -270,7 +205,7 @@ extern "C" int ma_texture_maps(ma_ctx* ctx, const void* img, int dtype, int H, i
         rc = MA_EHIP;
     }
     if (rc == MA_OK) {
-        hipLaunchKernelGGL(tx_setup_kernel, dim3(1), dim3(256), 0, ctx->stream, taps, r, aux);
+        hipLaunchKernelGGL(wf_setup_kernel<>, dim3(1), dim3(256), 0, ctx->stream, taps, r, aux);
         switch (dtype) {
         case MA_U8: rc = tx_launch<unsigned char>(ctx, img, H, W, r, aux, ws, o); break;
         case MA_U16: rc = tx_launch<unsigned short>(ctx, img, H, W, r, aux, ws, o); break;

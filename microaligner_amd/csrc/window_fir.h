@@ -1,0 +1,152 @@
+// The separable window FIR behind the flow smoothing, the texture maps and the flow refinement (flow_smooth.hip, texture.hip,
+// flow_refine.hip): its tile, stated once.  Off the measured path: nothing in register() or warp() reaches it (a header of
+// single sources, build.SOURCE_HEADERS).
+//
+// A symmetric FIR with up to 2 * WF_MAX_RADIUS + 1 taps over P planes, in two launches through a workspace of 4 P B/px that
+// holds the row pass's planes TRANSPOSED ((W, H) each).  Both passes are then the same tile: 64 lines (lanes) x WF_S = WF_NW *
+// WF_R outputs along the filtered axis, which is the fast axis of what the pass reads.
+//   - staging: a wave reads a line's span (outputs + r halo + guards) with consecutive lanes on consecutive elements
+//     (coalesced: loads of the user's arrays in the row pass, float loads of a transposed plane in the column pass) into
+//     LDS [64 lines][pitch], pitch odd, so that these writes and the filter's reads (lane = line) are free of bank conflicts;
+//   - filter: a thread slides a register window along its line for WF_R consecutive outputs (d_sym_fir_slide_pk, the
+//     window blurs' and DOG's filter), in the accumulation order of the users' headers, one plane after the other through the
+//     same LDS tile;
+//   - output: lane = line, and a line of the input is a column of the output, so the stores are coalesced as well: the row
+//     pass writes its planes transposed, the column pass ends in the user's own epilogue and writes row-major.
+// What is stated here: the tile's constants, the tap table and its setup, one plane of a row pass (wf_row_plane) and the host
+// side of a call.  The column kernels, and the row kernel of the flow smoothing, stage and filter in their own bodies, in the
+// words of wf_row_plane: they were compiled as one body, and taken out into a function they compile to other code.
+// One kernel family for every r in 1 .. 128: LDS is sized by r at launch (40 KiB at r = 12, 97 KiB at r = 128).
+// Bound by the instructions it issues (two LDS reads and three packed operations per tap and 16 outputs), like the window
+// blurs, not by bytes; at large r the halo (2r staged elements beside 128 outputs per line) adds to it.
+#pragma once
+#include "ma_internal.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int WF_NW = 8, WF_R = 16, WF_S = WF_NW * WF_R;   // waves per block, outputs per thread, outputs per line and block
+constexpr int WF_G = 2;                                     // guard elements either side of the halo (d_sym_fir_slide_pk)
+constexpr int WF_MAX_RADIUS = 128;
+constexpr int WF_TAPS = 8 + WF_MAX_RADIUS + 8;              // floats of a tap table in the MA_TAP layout
+
+// elements of a staged line, and the pitch of the lines in LDS (the kernels state both in place)
+inline int wf_span(int r) { return WF_S + 2 * r + 2 * WF_G; }
+inline int wf_pitch(int r) { return wf_span(r) | 1; }
+
+struct WfTaps { float t[WF_MAX_RADIUS + 1]; };   // k[0 .. r], the rest 0; passed to a setup kernel by value
+
+// element i < WF_TAPS of the taps in the MA_TAP layout
+__device__ __forceinline__ void wf_layout_tap(const WfTaps& taps, int r, int i, float* __restrict__ aux)
+{
+    float v = 0.f;
+    if (i == 0) v = taps.t[0];
+    else if (i >= 8 && i - 7 <= r) v = taps.t[i - 7];
+    aux[i] = v;
+}
+
+// aux[0 .. WF_TAPS): the taps in the MA_TAP layout; one block.  A template only so that a source with a setup kernel of its
+// own (flow_smooth.hip) does not carry this one.
+template <int = 0>
+__global__ __launch_bounds__(256) void wf_setup_kernel(WfTaps taps, int r, float* __restrict__ aux)
+{
+    if (threadIdx.x < WF_TAPS) wf_layout_tap(taps, r, threadIdx.x, aux);
+}
+
+// One plane of the row pass through the block's LDS tile [64][pitch].  Block: rows [y0, y0 + 64) x output columns
+// [x0, x0 + WF_S); lane = row, wv = wave (wave-uniform).  at(H, W, x, y): the plane's value at a pixel inside the image,
+// outside it the value is 0; H and W reach it from here, so that the compiler knows them for those of the guard.
+// dst: the plane's (W, H) array.
+template <class At>
+__device__ __forceinline__ void wf_row_plane(At at, int H, int W, int r, const float* __restrict__ taps, int x0, int y0,
+                                             int lane, int wv, float* lds, float* __restrict__ dst)
+{
+    const int span = WF_S + 2 * r + 2 * WF_G, pitch = span | 1;
+    for (int row = wv; row < 64; row += WF_NW) {
+        const int y = y0 + row;
+        float* line = lds + row * pitch;
+        for (int c = lane; c < span; c += 64) {
+            const int x = x0 - r - WF_G + c;
+            line[c] = (y < H && x >= 0 && x < W) ? at(H, W, x, y) : 0.f;
+        }
+    }
+    __syncthreads();
+    float acc[WF_R];
+    d_sym_fir_slide_pk<WF_R, false, false>(lds + lane * pitch, WF_G + r + wv * WF_R, r, taps, acc);
+    __syncthreads();
+    const int y = y0 + lane;
+#pragma unroll
+    for (int q = 0; q < WF_R; q++) {
+        const int x = x0 + wv * WF_R + q;
+        if (x < W && y < H) dst[(size_t)x * H + y] = acc[q];
+    }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------
+// the caller's taps k[0 .. r], checked
+inline int wf_taps(const float* host, int r, WfTaps* taps)
+{
+    *taps = WfTaps{};
+    for (int k = 0; k <= r; k++) {
+        MA_REQUIRE(std::isfinite(host[k]) && host[k] >= 0.f, "taps must be finite and not negative");
+        taps->t[k] = host[k];
+    }
+    MA_REQUIRE(taps->t[0] > 0.f, "the centre tap must be positive");
+    return MA_OK;
+}
+
+// blocks of a 1-D grid over nbx x nby tiles; what: "flow" or "image", for the refusal
+inline int wf_grid(long long nbx, long long nby, const char* what, unsigned* blocks)
+{
+    if (nbx * nby > 0x7fffffffLL) {
+        ma_set_error("invalid argument: %s too large", what);
+        return MA_EINVAL;
+    }
+    *blocks = (unsigned)(nbx * nby);
+    return MA_OK;
+}
+
+// how the two passes over an (H, W) image are launched at radius r: 64 * WF_NW threads, lds bytes of dynamic LDS
+struct WfShape {
+    size_t lds;
+    int nbx_row, nbx_col;      // tiles along x of the row and of the column pass (the kernels' nbx)
+    unsigned g_row, g_col;     // blocks
+};
+
+// the shape, and the opt-in of the row and the column kernel to its LDS where that is above 64 KiB
+inline int wf_shape(int H, int W, int r, const char* what, const void* row, const void* col, WfShape* s)
+{
+    s->lds = (size_t)64 * wf_pitch(r) * sizeof(float);
+    s->nbx_row = (W + WF_S - 1) / WF_S;
+    s->nbx_col = (W + 63) / 64;
+    MA_TRY(wf_grid(s->nbx_row, (H + 63) / 64, what, &s->g_row));
+    MA_TRY(wf_grid(s->nbx_col, (H + WF_S - 1) / WF_S, what, &s->g_col));
+    if (s->lds > 64 * 1024) {
+        MA_HIP(hipFuncSetAttribute(row, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds));
+        MA_HIP(hipFuncSetAttribute(col, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds));
+    }
+    return MA_OK;
+}
+
+// the device counters of a call (n of them, zeroed) in the ctx workspace, if the caller asked for counts
+inline int wf_counters(ma_ctx* ctx, bool wanted, int n, unsigned long long** counter)
+{
+    *counter = nullptr;
+    if (!wanted) return MA_OK;
+    MA_TRY(ma_ws_reserve(ctx, n * sizeof(unsigned long long)));
+    MA_TRY(ma_pinned_reserve(ctx, n * sizeof(unsigned long long)));
+    *counter = (unsigned long long*)ctx->ws;
+    MA_HIP(hipMemsetAsync(*counter, 0, n * sizeof(unsigned long long), ctx->stream));
+    return MA_OK;
+}
+
+inline int wf_read_counters(ma_ctx* ctx, const unsigned long long* counter, int n, long long* host)
+{
+    MA_HIP(hipMemcpyAsync(ctx->pinned, counter, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    MA_HIP(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; k++) host[k] = (long long)((const unsigned long long*)ctx->pinned)[k];
+    return MA_OK;
+}
+
+} // namespace

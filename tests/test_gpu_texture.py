@@ -239,4 +239,5 @@ def test_the_source_hash_is_the_parents():
     from microaligner_amd import build
     assert build.source_hash() == "7f5e1df0cf7595ec" == _lib.source_hash()
     assert "texture.hip" in build.SOURCES and "microaligner_texture.h" not in " ".join(build.HEADERS)
-    assert [os.path.basename(h) for h in build.SOURCE_HEADERS["texture.hip"]] == ["microaligner_texture.h", "cell_grid.h"]
+    assert [os.path.basename(h) for h in build.SOURCE_HEADERS["texture.hip"]] == ["microaligner_texture.h", "cell_grid.h",
+                                                                                  "window_fir.h"]

@@ -5,7 +5,7 @@
     python tools/kernel_asm.py compare OLD NEW     per kernel: instruction stream and .amdhsa_* descriptor, OLD against NEW
 
 `compare` splits each file at the kernels' function labels, so that a kernel may move within its file, masks what only
-numbers the functions of a file (.LBB<n>_, .Lfunc_end<n>) and the per-compilation __hip_cuid_<hex> symbol, and exits non-zero if a kernel of OLD is missing
+numbers the functions of a file (.LBB<n>_, BB<n>_ in the loop comments and their padding, .Lfunc_end<n>) and the per-compilation __hip_cuid_<hex> symbol, and exits non-zero if a kernel of OLD is missing
 from NEW or differs, or if a file without kernels differs at all.  Kernels that only NEW has are listed, not counted.
 """
 import os
@@ -15,7 +15,9 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MASK = [(re.compile(r"__hip_cuid_[0-9a-f]+"), "__hip_cuid_"), (re.compile(r"\.L([A-Za-z_]+?)\d+(?=_|\b)"), r".L\1")]
+MASK = [(re.compile(r"__hip_cuid_[0-9a-f]+"), "__hip_cuid_"), (re.compile(r"\.L([A-Za-z_]+?)\d+(?=_|\b)"), r".L\1"),
+        # the loop comments name blocks without the .L, and stand in a column padded behind the numbered label
+        (re.compile(r"\bBB\d+_(?=\d)"), "BB_"), (re.compile(r"[ \t]+;"), " ;")]
 
 
 def dump(out, tree=ROOT):
