@@ -15,6 +15,7 @@ from .optflow_reg import OptFlowRegistrator, TileFlowCalc, Warper, farneback, co
 from .shared_modules.registration_qc import FlowQC, RegistrationQC, assess_registration, flow_qc
 from .shared_modules.residual_shift import ResidualShift, ShiftMaps, residual_shift
 from .shared_modules.texture import TextureMaps, texture_maps
+from .shared_modules.local_correlation import CorrelationMaps, local_correlation
 from .shared_modules.normalize import NormalizeInfo, normalize_percentile
 from .shared_modules.utils import max_project_and_normalize, pad_to_shape, transform_img_with_tmat
 
@@ -24,5 +25,5 @@ __all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc",
            "smooth_flow", "fold_mask", "repair_flow", "fit_flow_affine", "split_flow", "join_flow", "local_affine", "FlowAffineInfo",
            "FlowAffineMaps", "texture_maps", "TextureMaps", "align_affine", "DirectAffineInfo", "refine_flow", "FlowRefineInfo",
            "LandmarkFit", "fit_landmarks", "landmark_flow", "landmark_points", "align_translation", "TranslationInfo",
-           "normalize_percentile", "NormalizeInfo"]
+           "normalize_percentile", "NormalizeInfo", "local_correlation", "CorrelationMaps"]
 __version__ = "0.1.0"

@@ -268,6 +268,14 @@ QUANTILE_SIGNATURES = {
     "ma_normalize_range_u8": (_i, [_vp, _vp, _i, _sz, _d, _d, _vp]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_localcorr.h (local correlation maps of a
+# registered pair)
+MA_LOCALCORR_MAX_RADIUS, MA_LOCALCORR_CLASSES = 128, 4
+LOCALCORR_SIGNATURES = {
+    "ma_local_correlation": (_i, [_vp, _vp, _i, _vp, _i, _i, C.POINTER(_f), _i, _f, _f, _f, _vp, _i, _f, _f, _f, _vp, _vp,
+                                  _i, _i, C.POINTER(C.c_longlong)]),
+}
+
 _lib = None
 
 
@@ -287,7 +295,7 @@ def load():
             list(FLOWAFFINE_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + \
             list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()) + \
             list(LANDMARK_SIGNATURES.items()) + list(TRANSLATION_SIGNATURES.items()) + \
-            list(QUANTILE_SIGNATURES.items()):
+            list(QUANTILE_SIGNATURES.items()) + list(LOCALCORR_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

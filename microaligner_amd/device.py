@@ -401,6 +401,67 @@ def flow_refine_step_params(ref, warped, flow, taps, floor, weight=None, max_ste
     return H, W, rdt, taps, r, floor, kind, max_step
 
 
+# ---- local correlation maps of a registered pair (include/microaligner_localcorr.h) ----------------------------------------
+LOCALCORR_PLANES = ("score", "weight")
+
+
+def _finite_f32(v, name):
+    x = _real(v, name)
+    with np.errstate(over="ignore"):
+        x = np.float32(x)
+    if not np.isfinite(x):
+        raise ValueError(f"{name} must be finite as float32, got {v!r}")
+    return float(x)
+
+
+def local_correlation_params(ref, img, taps, floor, center=(0.0, 0.0), weight=None, lo=0.25, hi=0.75, min_support=0.0,
+                             cell_size=None, want=("score",)):
+    """Checks and host-side arguments of the local correlation maps (include/microaligner_localcorr.h) without touching a
+    device: (H, W, ref dtype code, taps as C-contiguous float32, r, (center_ref, center_img), floor, weight kind,
+    min_support, lo, hi -- all as float32 --, cell_h, cell_w or None twice, want as a tuple).  ref: an (H, W) uint8, uint16
+    or float32 array (numpy or device); img: (H, W) float32; weight: None, or an (H, W) float32 map or uint8 mask; want: which
+    of "score" and "weight" to make.  ValueError for anything the C entry would refuse."""
+    rdt = _check_image(ref, "ref")
+    H, W = (int(v) for v in ref.shape)
+    if not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
+        raise ValueError(f"image sides must be in [1, 2^24], got {(H, W)}")
+    if not isinstance(img, (np.ndarray, DeviceArray)) or img.dtype != np.float32 or tuple(img.shape) != (H, W):
+        raise ValueError(f"img must be float32 of shape {(H, W)}, got {getattr(img, 'dtype', None)} "
+                         f"{tuple(getattr(img, 'shape', ()))}")
+    taps, r = _check_taps(taps)
+    floor = _positive_f32(floor, "floor")
+    try:
+        ca, cb = center
+    except (TypeError, ValueError):
+        raise ValueError(f"center must be a pair of numbers, got {center!r}") from None
+    ca, cb = _finite_f32(ca, "center[0]"), _finite_f32(cb, "center[1]")
+    ms = _finite_f32(min_support, "min_support")
+    if not ms >= 0:
+        raise ValueError(f"min_support must not be negative, got {min_support!r}")
+    lo, hi = _finite_f32(lo, "lo"), _finite_f32(hi, "hi")
+    if not -1.0 <= lo < hi <= 1.0:
+        raise ValueError(f"lo and hi must satisfy -1 <= lo < hi <= 1 as float32, got {lo!r}, {hi!r}")
+    kind = L.MA_SMOOTH_WEIGHT_NONE
+    if weight is not None:
+        wshape, wdtype = tuple(getattr(weight, "shape", ())), getattr(weight, "dtype", None)
+        if not isinstance(weight, (np.ndarray, DeviceArray)):
+            raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
+        if wshape == (H, W) and wdtype == np.float32:
+            kind = L.MA_SMOOTH_WEIGHT_F32
+        elif wshape == (H, W) and wdtype == np.uint8:
+            kind = L.MA_SMOOTH_WEIGHT_U8
+        else:
+            raise ValueError(f"the weight must be per pixel, float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+    if isinstance(want, str) or not all(isinstance(n, str) and n in LOCALCORR_PLANES for n in want) or \
+            len(set(want)) != len(tuple(want)):
+        raise ValueError(f"want must name distinct planes among {LOCALCORR_PLANES}, got {want!r}")
+    want = tuple(want)
+    ch, cw = (None, None) if cell_size is None else _cell_size_hw(cell_size)
+    if not want and cell_size is None:
+        raise ValueError("no output was asked for")
+    return H, W, rdt, taps, r, (ca, cb), floor, kind, ms, lo, hi, ch, cw, want
+
+
 # ---- global translation search (include/microaligner_translation.h) --------------------------------------------------------
 def translation_params(ref, mov, window, exclude=0):
     """Checks and host-side arguments of the translation search (include/microaligner_translation.h) without touching a
@@ -1491,6 +1552,30 @@ class Context:
         self._run(self.lib.ma_texture_maps, img.ptr, dtype, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r,
                   0.0 if floor is None else floor, ptr["lam_min"], ptr["lam_max"], ptr["weight"], ch or 0, cw or 0,
                   None if counts is None else counts.ctypes.data_as(C.POINTER(C.c_longlong)))
+        if counts is not None:
+            out["counts"] = counts
+        return out
+
+    def local_correlation(self, ref, img, taps, floor, center=(0.0, 0.0), weight=None, lo=0.25, hi=0.75, min_support=0.0,
+                          cell_size=None, want=("score",)):
+        """The local correlation maps of an (H, W) uint8, uint16 or float32 device image `ref` and an (H, W) float32 device
+        image `img` on its grid, with the symmetric kernel taps t[0 .. r] (include/microaligner_localcorr.h): the windowed
+        ZNCC of ref - center[0] and img - center[1] with `floor` (in squared grey levels) under both variances, NaN where
+        the window's weight is not above min_support; the weight that is 0 below `lo`, 1 from `hi` on and linear between;
+        and, with cell_size, the per-cell counts of agreeing, disagreeing, flat and unsupported pixels.  weight: None, an
+        (H, W) float32 map or uint8 mask.  -> a dict of the planes named in `want` ((H, W) float32 device arrays) and, with
+        cell_size, "counts": a (gy, gx, 4) int64 numpy array, at the cost of a synchronisation."""
+        H, W, rdt, taps, r, (ca, cb), floor, kind, ms, lo, hi, ch, cw, want = local_correlation_params(
+            ref, img, taps, floor, center, weight, lo, hi, min_support, cell_size, want)
+        out = {n: self.empty((H, W), np.float32) for n in want}
+        ptr = {n: (out[n].ptr if n in out else None) for n in LOCALCORR_PLANES}
+        counts = None
+        if ch is not None:
+            gy, gx = self._cell_grid_shape(H, W, min(ch, H), min(cw, W))
+            counts = np.empty((gy, gx, L.MA_LOCALCORR_CLASSES), np.int64)
+        self._run(self.lib.ma_local_correlation, ref.ptr, rdt, img.ptr, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r,
+                  ca, cb, floor, None if weight is None else weight.ptr, kind, ms, lo, hi, ptr["score"], ptr["weight"],
+                  ch or 0, cw or 0, None if counts is None else counts.ctypes.data_as(C.POINTER(C.c_longlong)))
         if counts is not None:
             out["counts"] = counts
         return out
