@@ -276,6 +276,15 @@ LOCALCORR_SIGNATURES = {
                                   _i, _i, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_flowmedian.h (median filter of a flow, outlier
+# mask); the weight kinds are those of microaligner_flowsmooth.h
+MA_MEDIAN_ALL, MA_MEDIAN_OUTLIERS = 0, 1        # enum ma_median_mode
+MA_MEDIAN_GENERIC = 1                           # enum ma_median_flags
+MA_MEDIAN_MAX_RADIUS = 7
+FLOWMEDIAN_SIGNATURES = {
+    "ma_median_flow": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, C.POINTER(C.c_longlong)]),
+}
+
 _lib = None
 
 
@@ -295,7 +304,7 @@ def load():
             list(FLOWAFFINE_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + \
             list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()) + \
             list(LANDMARK_SIGNATURES.items()) + list(TRANSLATION_SIGNATURES.items()) + \
-            list(QUANTILE_SIGNATURES.items()) + list(LOCALCORR_SIGNATURES.items()):
+            list(QUANTILE_SIGNATURES.items()) + list(LOCALCORR_SIGNATURES.items()) + list(FLOWMEDIAN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
            "flow_compose.hip", "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip", "texture.hip", "direct_affine.hip", "flow_refine.hip",
-           "landmarks.hip", "translation.hip", "quantile.hip", "local_correlation.hip"]
+           "landmarks.hip", "translation.hip", "quantile.hip", "local_correlation.hip", "flow_median.hip"]
 HEADERS = [os.path.join(CSRC, "ma_internal.h"), os.path.join(CSRC, "remap_common.h"), os.path.join(CSRC, "nmi_score.h"),
            os.path.join(HERE, "..", "include", "microaligner_hip.h")]
 # headers of single sources that are off the measured path (not in HEADERS, so not in source_hash())
@@ -47,7 +47,9 @@ SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_q
                   "quantile.hip": [os.path.join(HERE, "..", "include", "microaligner_quantile.h")],
                   "local_correlation.hip": [os.path.join(HERE, "..", "include", "microaligner_localcorr.h"),
                                             os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID,
-                                            _WINDOW_FIR]}
+                                            _WINDOW_FIR],
+                  "flow_median.hip": [os.path.join(HERE, "..", "include", "microaligner_flowmedian.h"),
+                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h")]}
 # the grid-flow headers are also read by the two sources whose kernels take their flow from a grid: further dependencies of
 # those sources, beside the headers of their own above
 GRID_FLOW_USERS = {"warp_compose.hip": _FLOW_GRID, "flow_invert.hip": _FLOW_GRID}
@@ -110,6 +112,7 @@ def source_hash():
     #   - the radix select of an image's order statistics and the scaling to u8 between two given values, which only
     #     image_quantiles() / normalize_percentile() / a `percentiles` argument reach;
     #   - the local correlation maps (windowed ZNCC of a registered pair), which only local_correlation() reaches;
+    #   - the median filter of a flow and its outlier mask, which only median_flow() / outlier_mask() reach;
     #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps, flow_jacobian.h, det J of
     #     the quality maps and the fold mask, and window_fir.h, the separable FIR tile of the flow smoothing, the texture
     #     maps, the flow refinement and the local correlation maps (SOURCE_HEADERS).
@@ -117,7 +120,7 @@ def source_hash():
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
                 "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip",
                 "texture.hip", "direct_affine.hip", "flow_refine.hip", "landmarks.hip", "translation.hip",
-                "quantile.hip", "local_correlation.hip"}
+                "quantile.hip", "local_correlation.hip", "flow_median.hip"}
     for path in [os.path.join(CSRC, s) for s in SOURCES if s not in off_path] + HEADERS:
         h.update(open(path, "rb").read())
     h.update(" ".join(_flags()).encode())

@@ -177,6 +177,29 @@ def _cell_size_hw(cell_size):
     return int(ch), int(cw)
 
 
+def _weight_kind(weight, cell_size, H, W):
+    """(kind, cell_h, cell_w) of a smooth_flow-style weight: None; an (H, W) float32 or uint8 array (numpy or device); or,
+    with cell_size, a (gy, gx) float32 map on that cell grid."""
+    if weight is None:
+        if cell_size is not None:
+            raise ValueError("cell_size only has a meaning together with a per-cell weight")
+        return L.MA_SMOOTH_WEIGHT_NONE, 1, 1
+    if not isinstance(weight, (np.ndarray, DeviceArray)):
+        raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
+    wshape, wdtype = tuple(weight.shape), weight.dtype
+    if cell_size is not None:
+        ch, cw = _cell_size_hw(cell_size)
+        want = (-(-H // ch), -(-W // cw))
+        if wdtype != np.float32 or wshape != want:
+            raise ValueError(f"a per-cell weight of cells {(ch, cw)} must be float32 of shape {want}, got {wdtype} {wshape}")
+        return L.MA_SMOOTH_WEIGHT_CELLS, ch, cw
+    if wshape == (H, W) and wdtype == np.float32:
+        return L.MA_SMOOTH_WEIGHT_F32, 1, 1
+    if wshape == (H, W) and wdtype == np.uint8:
+        return L.MA_SMOOTH_WEIGHT_U8, 1, 1
+    raise ValueError(f"a per-pixel weight must be float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+
+
 def smooth_flow_params(flow, taps, weight=None, cell_size=None, where="all", min_support=0.0):
     """Checks and host-side arguments of the weighted smoothing (include/microaligner_flowsmooth.h) without touching a
     device: (H, W, taps as C-contiguous float32, r, weight kind, cell_h, cell_w, mode, min_support as float32).
@@ -191,26 +214,7 @@ def smooth_flow_params(flow, taps, weight=None, cell_size=None, where="all", min
         ms = np.float32(ms)
     if not (np.isfinite(ms) and ms >= 0):
         raise ValueError(f"min_support must be finite and not negative as float32, got {min_support!r}")
-    kind, ch, cw = L.MA_SMOOTH_WEIGHT_NONE, 1, 1
-    if weight is None:
-        if cell_size is not None:
-            raise ValueError("cell_size only has a meaning together with a per-cell weight")
-    else:
-        wshape, wdtype = tuple(getattr(weight, "shape", ())), getattr(weight, "dtype", None)
-        if not isinstance(weight, (np.ndarray, DeviceArray)):
-            raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
-        if cell_size is not None:
-            ch, cw = _cell_size_hw(cell_size)
-            want = (-(-H // ch), -(-W // cw))
-            if wdtype != np.float32 or wshape != want:
-                raise ValueError(f"a per-cell weight of cells {(ch, cw)} must be float32 of shape {want}, got {wdtype} {wshape}")
-            kind = L.MA_SMOOTH_WEIGHT_CELLS
-        elif wshape == (H, W) and wdtype == np.float32:
-            kind = L.MA_SMOOTH_WEIGHT_F32
-        elif wshape == (H, W) and wdtype == np.uint8:
-            kind = L.MA_SMOOTH_WEIGHT_U8
-        else:
-            raise ValueError(f"a per-pixel weight must be float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+    kind, ch, cw = _weight_kind(weight, cell_size, H, W)
     return H, W, taps, r, kind, ch, cw, SMOOTH_MODES[where], float(ms)
 
 
@@ -220,6 +224,38 @@ def fold_mask_params(flow, margin):
     if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or not 0 <= int(margin) <= L.MA_FOLD_MASK_MAX_MARGIN:
         raise ValueError(f"margin must be an integer in [0, {L.MA_FOLD_MASK_MAX_MARGIN}], got {margin!r}")
     return H, W, int(margin)
+
+
+# ---- median filter of a flow, outlier mask (include/microaligner_flowmedian.h) ---------------------------------------------
+MEDIAN_MODES = {"all": L.MA_MEDIAN_ALL, "outliers": L.MA_MEDIAN_OUTLIERS}
+
+
+def median_flow_params(flow, radius=2, weight=None, cell_size=None, where="all", thresh=None, generic=False):
+    """Checks and host-side arguments of the median filter (include/microaligner_flowmedian.h) without touching a device:
+    (H, W, r, weight kind, cell_h, cell_w, mode, thresh as float32, flags).  weight: what it is for smooth_flow, read as a
+    mask.  thresh: None stands for +Inf ("no outliers") and is refused with where="outliers".  ValueError for anything the
+    C entry would refuse."""
+    H, W = _check_flow(flow)
+    if -(-H // 32) * -(-W // 64) > 0x7fffffff:
+        raise ValueError(f"flow too large: more than 2^31 - 1 tiles of 32 x 64 pixels in {(H, W)}")
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= L.MA_MEDIAN_MAX_RADIUS:
+        raise ValueError(f"radius must be an integer in [1, {L.MA_MEDIAN_MAX_RADIUS}], got {radius!r}")
+    if not isinstance(where, str) or where not in MEDIAN_MODES:
+        raise ValueError(f"unknown mode {where!r}: expected one of {sorted(MEDIAN_MODES)}")
+    if thresh is None:
+        if where == "outliers":
+            raise ValueError('where="outliers" needs a thresh')
+        th = np.float32(np.inf)
+    else:
+        th = _real(thresh, "thresh")
+        with np.errstate(over="ignore"):
+            th = np.float32(th)
+        if not th >= 0:
+            raise ValueError(f"thresh must not be NaN or negative, got {thresh!r}")
+    if not isinstance(generic, (bool, np.bool_)):
+        raise ValueError(f"generic must be a bool, got {generic!r}")
+    kind, ch, cw = _weight_kind(weight, cell_size, H, W)
+    return H, W, int(radius), kind, ch, cw, MEDIAN_MODES[where], float(th), L.MA_MEDIAN_GENERIC if generic else 0
 
 
 # ---- texture support maps of an image (include/microaligner_texture.h) ----------------------------------------------------
@@ -545,6 +581,12 @@ class SmoothInfo(collections.namedtuple("SmoothInfo", "unsupported")):
 class FoldInfo(collections.namedtuple("FoldInfo", "folded invalid dropped")):
     """fold_mask(..., return_info=True): pixels with a finite det J <= 0, pixels with a non-finite component (the sums of
     flow_qc's maps), and pixels the mask drops (keep == 0)."""
+
+
+class MedianInfo(collections.namedtuple("MedianInfo", "outliers dropped unsupported")):
+    """median_flow(..., return_info=True): participating pixels farther than thresh from the median of their window,
+    pixels that do not participate (weight or value), and those of them whose window holds no participating pixel at all
+    (their median is NaN)."""
 
 
 class RepairInfo(collections.namedtuple("RepairInfo", "rounds converged")):
@@ -1535,6 +1577,40 @@ class Context:
         counts = (C.c_longlong * 3)()
         self._run(self.lib.ma_flow_fold_mask, flow.ptr, H, W, margin, keep.ptr, counts if return_info else None)
         return (keep, FoldInfo(*(int(v) for v in counts))) if return_info else keep
+
+    def median_flow(self, flow, radius=2, weight=None, cell_size=None, where="all", thresh=None, return_info=False, out=None,
+                    keep=False, generic=False):
+        """The median filter of a flow over (2 radius + 1)^2 windows and its outlier mask
+        (include/microaligner_flowmedian.h), in one kernel.  Device arrays in (weight: None, an (H, W) float32 or uint8
+        array, or with cell_size a (gy, gx) float32 map; read as a mask), new device arrays out.
+        out: None -- a new (H, W, 2) array; a DeviceArray to write instead (never `flow` itself: a median reads its
+        neighbours); False -- no flow is made (keep only).  keep: False -- no mask; True -- a new (H, W) uint8 array; or a
+        DeviceArray to write.  generic: take the kernel that serves every radius, also where radius <= 3 (same bits).
+        Returns what was made, in the order out, keep, and with return_info a MedianInfo(outliers, dropped, unsupported)
+        at the cost of a synchronisation: one object alone, or a tuple of them."""
+        H, W, r, kind, ch, cw, mode, th, flags = median_flow_params(flow, radius, weight, cell_size, where, thresh, generic)
+        if out is flow:
+            raise ValueError("out must not be the flow: a median reads its neighbours")
+        if out is False and keep is False:
+            raise ValueError("nothing to make: out=False needs a keep")
+        if out is not None and out is not False and \
+                (not isinstance(out, DeviceArray) or out.dtype != np.float32 or out.shape != (H, W, 2)):
+            raise ValueError(f"out must be a float32 DeviceArray of shape {(H, W, 2)}, None or False")
+        if not isinstance(keep, bool) and \
+                (not isinstance(keep, DeviceArray) or keep.dtype != np.uint8 or keep.shape != (H, W)):
+            raise ValueError(f"keep must be a uint8 DeviceArray of shape {(H, W)} or a bool")
+        if out is None:
+            out = self.empty((H, W, 2), np.float32)
+        if keep is True:
+            keep = self.empty((H, W), np.uint8)
+        counts = (C.c_longlong * 3)()
+        self._run(self.lib.ma_median_flow, flow.ptr, H, W, r, None if weight is None else weight.ptr, kind, ch, cw, mode, th,
+                  flags, None if out is False else out.ptr, None if keep is False else keep.ptr,
+                  counts if return_info else None)
+        res = [a for a in (out, keep) if a is not False]
+        if return_info:
+            res.append(MedianInfo(*(int(v) for v in counts)))
+        return res[0] if len(res) == 1 else tuple(res)
 
     def texture_maps(self, img, taps, floor=None, cell_size=None, want=("lam_min", "lam_max")):
         """The texture support maps of an (H, W) uint8, uint16 or float32 device image with the symmetric kernel taps
