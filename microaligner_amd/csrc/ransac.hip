@@ -148,7 +148,9 @@ __global__ __launch_bounds__(RS_F) void rs_ratio_compact(const int* __restrict__
         bool good = false;
         int j = 0;
         if (q < nq) {
-            const float r0 = __fsqrt_rn(d2[2 * q]), r1 = __fsqrt_rn(d2[2 * q + 1]);
+            // sqrtf: the correctly rounded root, np.sqrt's (__fsqrt_rn is the 1 ulp v_sqrt_f32 here: near the threshold it
+            // counted other matches than the host statement)
+            const float r0 = sqrtf(d2[2 * q]), r1 = sqrtf(d2[2 * q + 1]);
             good = r0 < ratio * r1;
             j = idx[2 * q];
             if (good && (unsigned)j >= (unsigned)nt) good = false;     // cannot happen with indices from the search
@@ -191,7 +193,7 @@ __device__ __forceinline__ bool rs_ratio_good(const int* __restrict__ idx, const
 {
     j = 0;
     if (q >= nq) return false;
-    const float r0 = __fsqrt_rn(d2[2 * q]), r1 = __fsqrt_rn(d2[2 * q + 1]);
+    const float r0 = sqrtf(d2[2 * q]), r1 = sqrtf(d2[2 * q + 1]);       // (correctly rounded, as in rs_ratio_compact)
     j = idx[2 * q];
     return r0 < ratio * r1 && (unsigned)j < (unsigned)nt;
 }

@@ -2036,10 +2036,12 @@ class Context:
     _PCG64_STATES = {}
 
     def match_similarity(self, idx, dist_sq, query_pts, train_pts, ratio=0.5, confidence=0.99, reproj_threshold=3.0,
-                         max_iters=2000, seed=0):
+                         max_iters=2000, seed=0, n_train=None):
         """Ratio test + RANSAC similarity fit on the device (ma_match_similarity) over what knn2(on_device=True) left there:
         bit for bit feature_reg.sparse_cpu.estimate_affine_partial_2d(query points of the good matches, their train points).
-        query_pts / train_pts: (n, 2) float64 device buffers (x, y).  Returns (matrix (2, 3) float64 or None, n_good, status);
+        query_pts / train_pts: (n, 2) float64 device buffers (x, y).  n_train: the number of train points -- a match whose first
+        neighbour is not in [0, n_train) is not a good match; None: what train_pts holds, nbytes // 16 (a buffer of capacity
+        size then guards nothing: pass the count).  Returns (matrix (2, 3) float64 or None, n_good, status);
         status as in include/microaligner_hip.h: 0 ok, 1 fewer than 3 good matches, 2 no model, 3 not computed (use the host)."""
         st = self._PCG64_STATES.get(seed)
         if st is None:     # numpy's seeding (SeedSequence -> PCG64) stays numpy's: only the stream is restated in C
@@ -2050,8 +2052,13 @@ class Context:
         nq = int(idx.nbytes // 8)             # (nq, 2) int32, typed (knn2) or raw (tests)
         mat = (C.c_double * 6)()
         n_good, status = C.c_int(0), C.c_int(0)
+        nt = int(train_pts.nbytes // 16)
+        if n_train is not None:
+            if not 0 <= int(n_train) <= nt:
+                raise ValueError(f"n_train = {n_train} does not fit the train points buffer ({nt} points)")
+            nt = int(n_train)
         self._run(self.lib.ma_match_similarity, idx.ptr, dist_sq.ptr, nq, query_pts.ptr, train_pts.ptr,
-                  int(train_pts.nbytes // 16), float(ratio), float(confidence), float(reproj_threshold), int(max_iters), st, mat,
+                  nt, float(ratio), float(confidence), float(reproj_threshold), int(max_iters), st, mat,
                   C.byref(n_good), C.byref(status))
         m = np.array(mat, np.float64).reshape(2, 3) if status.value == 0 else None
         return m, n_good.value, status.value

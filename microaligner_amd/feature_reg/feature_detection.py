@@ -164,7 +164,7 @@ def match_features(img1_features: Features, img2_features: Features, verbose: bo
             return identity
         idx_d, dist_d = ctx.knn2(des2, des1, on_device=True)
         mat, n_good, status = ctx.match_similarity(idx_d, dist_d, img2_features.device_pts(ctx), img1_features.device_pts(ctx),
-                                                   ratio=RATIO, confidence=0.99)
+                                                   ratio=RATIO, confidence=0.99, n_train=len(des1))
         if status != 3:
             if verbose:
                 log("    Good matches", n_good, "/", len(des2))
