@@ -26,6 +26,8 @@ _FLOW_GRID = [os.path.join(HERE, "..", "include", "microaligner_flowgrid.h"), os
 _FLOW_JACOBIAN = os.path.join(CSRC, "flow_jacobian.h")   # det J, stated once for the quality maps and the fold mask
 # the separable FIR tile of the smoothing, the texture maps, the refinement and the local correlation maps
 _WINDOW_FIR = os.path.join(CSRC, "window_fir.h")
+# the weight argument of the six calls that take one: its readers on the device, its check and dispatch at the C entry
+_WEIGHT_MAP = os.path.join(CSRC, "weight_map.h")
 SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_qc.h"), _CELL_GRID, _FLOW_JACOBIAN],
                   "remap_interp.hip": _INTERP_HEADERS,
                   "warp_compose.hip": _INTERP_HEADERS + [os.path.join(HERE, "..", "include", "microaligner_compose.h")],
@@ -34,22 +36,22 @@ SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_q
                   "residual_shift.hip": [os.path.join(HERE, "..", "include", "microaligner_residual.h"), _CELL_GRID],
                   "flow_grid.hip": _FLOW_GRID + [_CELL_GRID],
                   "flow_smooth.hip": [os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID, _FLOW_JACOBIAN,
-                                      _WINDOW_FIR],
+                                      _WINDOW_FIR, _WEIGHT_MAP],
                   "flow_affine.hip": [os.path.join(HERE, "..", "include", "microaligner_flowaffine.h"),
-                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID],
+                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID, _WEIGHT_MAP],
                   "texture.hip": [os.path.join(HERE, "..", "include", "microaligner_texture.h"), _CELL_GRID, _WINDOW_FIR],
                   "direct_affine.hip": [os.path.join(HERE, "..", "include", "microaligner_direct.h"),
-                                        os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h")],
+                                        os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP],
                   "flow_refine.hip": [os.path.join(HERE, "..", "include", "microaligner_flowrefine.h"),
-                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WINDOW_FIR],
+                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WINDOW_FIR, _WEIGHT_MAP],
                   "landmarks.hip": [os.path.join(HERE, "..", "include", "microaligner_landmarks.h")],
                   "translation.hip": [os.path.join(HERE, "..", "include", "microaligner_translation.h")],
                   "quantile.hip": [os.path.join(HERE, "..", "include", "microaligner_quantile.h")],
                   "local_correlation.hip": [os.path.join(HERE, "..", "include", "microaligner_localcorr.h"),
                                             os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID,
-                                            _WINDOW_FIR],
+                                            _WINDOW_FIR, _WEIGHT_MAP],
                   "flow_median.hip": [os.path.join(HERE, "..", "include", "microaligner_flowmedian.h"),
-                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h")]}
+                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP]}
 # the grid-flow headers are also read by the two sources whose kernels take their flow from a grid: further dependencies of
 # those sources, beside the headers of their own above
 GRID_FLOW_USERS = {"warp_compose.hip": _FLOW_GRID, "flow_invert.hip": _FLOW_GRID}
@@ -114,8 +116,9 @@ def source_hash():
     #   - the local correlation maps (windowed ZNCC of a registered pair), which only local_correlation() reaches;
     #   - the median filter of a flow and its outlier mask, which only median_flow() / outlier_mask() reach;
     #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps, flow_jacobian.h, det J of
-    #     the quality maps and the fold mask, and window_fir.h, the separable FIR tile of the flow smoothing, the texture
-    #     maps, the flow refinement and the local correlation maps (SOURCE_HEADERS).
+    #     the quality maps and the fold mask, window_fir.h, the separable FIR tile of the flow smoothing, the texture
+    #     maps, the flow refinement and the local correlation maps, and weight_map.h, the weight argument of the six
+    #     calls above that take one (SOURCE_HEADERS).
     off_path = {"probe.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "affine.hip", "qc.hip",
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
                 "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip",

@@ -33,6 +33,18 @@ inline int ma_cell_grid(int h, int w, int cell_h, int cell_w, MaCellGrid* g, lon
     return MA_OK;
 }
 
+// the same grid as the struct of a kernel that counts per cell takes it (o->ch, o->cw, o->gx)
+template <class Out>
+int ma_cell_counts_grid(int h, int w, int cell_h, int cell_w, Out* o, long long* ncells)
+{
+    MaCellGrid g;
+    MA_TRY(ma_cell_grid(h, w, cell_h, cell_w, &g, ncells));
+    o->ch = g.ch;
+    o->cw = g.cw;
+    o->gx = g.gx;
+    return MA_OK;
+}
+
 // All cells in batches of at most `cap`, sized so that ws_per bytes of the device workspace per cell stay within the ctx's
 // workspace limit.  Per batch: enqueue(c0, nb, &dev, &bytes) launches the work of the cells [c0, c0 + nb) on the ctx stream
 // and names the device span that holds their results (at most pin_per bytes per cell); the span is copied to ctx->pinned,

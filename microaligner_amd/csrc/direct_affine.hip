@@ -9,7 +9,7 @@
 // shuffles, then the waves in order) and written as the tile's partial; da_final_kernel adds the partials in a fixed order.
 // No floating-point atomics: two calls give the same bits.
 #include "../../include/microaligner_direct.h"
-#include "ma_internal.h"
+#include "weight_map.h"
 
 #include <cmath>
 
@@ -97,11 +97,10 @@ __global__ __launch_bounds__(DA_T) void da_tile_kernel(const TR* __restrict__ re
                 const size_t q = (size_t)(int)fy * W + (size_t)(int)fx;
                 vi = ref[i];
                 v00 = mov[q], v01 = mov[q + 1], v10 = mov[q + W], v11 = mov[q + W + 1];
-                if (a.weight_kind == MA_SMOOTH_WEIGHT_F32) wgt = ((const float*)weight)[i];
-                else if (a.weight_kind == MA_SMOOTH_WEIGHT_U8) wgt = ((const unsigned char*)weight)[i] ? 1.f : 0.f;
+                wgt = d_weight_px(weight, a.weight_kind, i);
             }
             const bool finite = da_finite(vi) && da_finite(v00) && da_finite(v01) && da_finite(v10) && da_finite(v11);
-            const bool weighted = wgt > 0.f && wgt < INFINITY;
+            const bool weighted = d_weight_counts(wgt);
             const double tx = __dsub_rn(sx, fx), ty = __dsub_rn(sy, fy);
             const double a00 = (double)v00, a01 = (double)v01, a10 = (double)v10, a11 = (double)v11;
             const double d0 = __dsub_rn(a01, a00), d1 = __dsub_rn(a11, a10);
@@ -207,8 +206,7 @@ extern "C" int ma_direct_affine_moments(ma_ctx* ctx, const void* ref, int ref_dt
     MA_REQUIRE(ctx && ref && mov && M && sums_host && counts_host, "NULL argument");
     MA_REQUIRE(ref_dtype >= MA_U8 && ref_dtype <= MA_F32 && mov_dtype >= MA_U8 && mov_dtype <= MA_F32, "unknown dtype");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= DA_SIDE_MAX && W <= DA_SIDE_MAX, "image sides must be in [1, 2^24]");
-    MA_REQUIRE(weight_kind >= MA_SMOOTH_WEIGHT_NONE && weight_kind <= MA_SMOOTH_WEIGHT_U8, "the weight is none, a float32 map or a uint8 mask");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight, "NULL weight");
+    MA_TRY(ma_weight_check(weight, weight_kind, false, {}, 1, 1));   // writes host arrays only
     DaArgs a{};
     for (int k = 0; k < 6; k++) {
         MA_REQUIRE(std::isfinite(M[k]), "the matrix must be finite");

@@ -12,6 +12,7 @@
 // Apply: pointwise, 8 B in and 8 B out per pixel.
 #include "../../include/microaligner_flowaffine.h"
 #include "cell_grid.h"
+#include "weight_map.h"
 
 #include <cmath>
 
@@ -35,17 +36,15 @@ struct FaAcc {
     unsigned used, invalid, unweighted, trimmed;
 };
 
-__device__ __forceinline__ bool fa_finite(float v) { return fabsf(v) < INFINITY; }
-
 // one pixel of the header's section 1; wgt is weight(p)
 template <bool TRIM>
 __device__ __forceinline__ void fa_pixel(FaAcc& acc, int x, int y, double cx, double cy, float2 f, float wgt, const FaPrior& pr)
 {
-    if (!(fa_finite(f.x) && fa_finite(f.y))) {
+    if (!(d_finite(f.x) && d_finite(f.y))) {
         acc.invalid++;
         return;
     }
-    if (!(wgt > 0.f && wgt < INFINITY)) {
+    if (!d_weight_counts(wgt)) {
         acc.unweighted++;
         return;
     }
@@ -113,11 +112,7 @@ __global__ __launch_bounds__(FA_T) void fa_tile_kernel(const float* __restrict__
     const double cx = (double)(W - 1) * 0.5, cy = (double)(g.h - 1) * 0.5;
     // the per-cell weight: the cells of the map are the cells of this call, so a block reads one entry
     const float cell_w = KIND == MA_SMOOTH_WEIGHT_CELLS ? ((const float*)weight)[g.cell0 + blockIdx.y] : 1.f;
-    auto weight_at = [&](size_t i) -> float {
-        if (KIND == MA_SMOOTH_WEIGHT_F32) return ((const float*)weight)[i];
-        if (KIND == MA_SMOOTH_WEIGHT_U8) return ((const unsigned char*)weight)[i] ? 1.f : 0.f;
-        return cell_w;
-    };
+    auto weight_at = [&](size_t i) -> float { return KIND == MA_SMOOTH_WEIGHT_CELLS ? cell_w : d_weight_px(weight, KIND, i); };
 
     FaAcc acc{};
     for (int y = y0; y < y1; y++) {
@@ -197,8 +192,7 @@ extern "C" int ma_flow_affine_moments(ma_ctx* ctx, const float* flow, int H, int
 {
     MA_REQUIRE(ctx && flow && sums_host && counts_host, "NULL argument");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FA_SIDE_MAX && W <= FA_SIDE_MAX, "flow sides must be in [1, 2^24]");
-    MA_REQUIRE(weight_kind >= MA_SMOOTH_WEIGHT_NONE && weight_kind <= MA_SMOOTH_WEIGHT_CELLS, "unknown weight kind");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight, "NULL weight");
+    MA_TRY(ma_weight_check(weight, weight_kind, true, {}, cell_h, cell_w));   // writes host arrays only
     MA_REQUIRE(((size_t)flow & 7) == 0, "flow must be 8-byte aligned");
     FaPrior pr{};
     if (prior) {
@@ -223,12 +217,9 @@ extern "C" int ma_flow_affine_moments(ma_ctx* ctx, const float* flow, int H, int
             FaPart* res = part + (size_t)nb * ntiles;
             g.cell0 = c0;
             MaProfScope ps(ctx, MA_K_OTHER, (double)H * W * ((double)nb / ncells));
-            switch (weight_kind) {
-            case MA_SMOOTH_WEIGHT_F32: fa_launch<MA_SMOOTH_WEIGHT_F32>(ctx, flow, g, weight, ntx, (int)ntiles, nb, vec_ok, prior != nullptr, pr, part); break;
-            case MA_SMOOTH_WEIGHT_U8: fa_launch<MA_SMOOTH_WEIGHT_U8>(ctx, flow, g, weight, ntx, (int)ntiles, nb, vec_ok, prior != nullptr, pr, part); break;
-            case MA_SMOOTH_WEIGHT_CELLS: fa_launch<MA_SMOOTH_WEIGHT_CELLS>(ctx, flow, g, weight, ntx, (int)ntiles, nb, vec_ok, prior != nullptr, pr, part); break;
-            default: fa_launch<MA_SMOOTH_WEIGHT_NONE>(ctx, flow, g, weight, ntx, (int)ntiles, nb, vec_ok, prior != nullptr, pr, part); break;
-            }
+            ma_weight_dispatch(weight_kind, [&](auto kind) {
+                fa_launch<kind()>(ctx, flow, g, weight, ntx, (int)ntiles, nb, vec_ok, prior != nullptr, pr, part);
+            });
             hipLaunchKernelGGL(fa_cell_kernel, dim3(nb), dim3(FA_T), 0, ctx->stream, (const FaPart*)part, (int)ntiles, res);
             MA_HIP(hipGetLastError());
             *dev = res;

@@ -16,7 +16,7 @@
 // Both work on the integer keys: the result does not depend on how float min / max treat +-0 and denormals, and the
 // selection compiles to v_min_i32 / v_max_i32 / v_med3_i32.
 #include "../../include/microaligner_flowmedian.h"
-#include "ma_internal.h"
+#include "weight_map.h"
 
 #include <climits>
 #include <cmath>
@@ -27,23 +27,6 @@ constexpr int MF_SIDE_MAX = 1 << 24;
 constexpr int MF_TW = 64, MF_TH = 32, MF_ROWS = MF_TH / 4;   // the tile, and the rows of a wave (= pixels of a thread)
 constexpr int MF_REG_MAX_RADIUS = 3;                         // the largest radius of the register path
 constexpr int MF_MARK = INT_MAX;                             // the key of a NaN: no participating value has it
-
-struct MfWeight {
-    const void* p;
-    int ch, cw, gx;
-};
-
-__device__ __forceinline__ bool mf_finite(float v) { return fabsf(v) < INFINITY; }
-
-// weight(q) of the header; i = y * W + x
-template <int KIND>
-__device__ __forceinline__ float mf_weight_at(const MfWeight& wt, size_t i, int x, int y)
-{
-    if (KIND == MA_SMOOTH_WEIGHT_F32) return ((const float*)wt.p)[i];
-    if (KIND == MA_SMOOTH_WEIGHT_U8) return ((const unsigned char*)wt.p)[i] ? 1.f : 0.f;
-    if (KIND == MA_SMOOTH_WEIGHT_CELLS) return ((const float*)wt.p)[(size_t)(y / wt.ch) * wt.gx + x / wt.cw];
-    return 1.f;
-}
 
 // the header's key of a float's bits, and back (the map is its own inverse)
 __device__ __forceinline__ int mf_key(float v)
@@ -180,7 +163,7 @@ __device__ __forceinline__ int mf_window_bisect(const int2* base, int cols, int 
 // R = 0: the generic kernel, radius r; R >= 1: the register kernel of radius R (r is ignored).
 // counts: NULL, or {outliers, dropped, unsupported}.  out or keep may be NULL.
 template <int KIND, int R>
-__global__ __launch_bounds__(256) void mf_kernel(const float2* __restrict__ flow, int H, int W, MfWeight wt, int r_any, int mode,
+__global__ __launch_bounds__(256) void mf_kernel(const float2* __restrict__ flow, int H, int W, MaWeight wt, int r_any, int mode,
                                                  float thresh, int nbx, float2* __restrict__ out,
                                                  unsigned char* __restrict__ keep, unsigned long long* __restrict__ counts)
 {
@@ -197,8 +180,8 @@ __global__ __launch_bounds__(256) void mf_kernel(const float2* __restrict__ flow
         if (y >= 0 && y < H && x >= 0 && x < W) {
             const size_t i = (size_t)y * W + x;
             const float2 f = flow[i];
-            const float wgt = mf_weight_at<KIND>(wt, i, x, y);
-            if (wgt > 0.f && wgt < INFINITY && mf_finite(f.x) && mf_finite(f.y)) k = make_int2(mf_key(f.x), mf_key(f.y));
+            const float wgt = d_weight_at<KIND>(wt, i, x, y);
+            if (d_weight_counts(wgt) && d_finite(f.x) && d_finite(f.y)) k = make_int2(mf_key(f.x), mf_key(f.y));
         }
         tile[t] = k;
     }
@@ -250,7 +233,7 @@ __global__ __launch_bounds__(256) void mf_kernel(const float2* __restrict__ flow
 }
 
 template <int KIND, int R>
-static void mf_launch_one(ma_ctx* ctx, unsigned grid, const float* flow, int H, int W, const MfWeight& wt, int r, int mode,
+static void mf_launch_one(ma_ctx* ctx, unsigned grid, const float* flow, int H, int W, const MaWeight& wt, int r, int mode,
                           float thresh, int nbx, float* out, unsigned char* keep, unsigned long long* counts)
 {
     hipLaunchKernelGGL((mf_kernel<KIND, R>), dim3(grid), dim3(256), 0, ctx->stream, (const float2*)flow, H, W, wt, r, mode, thresh,
@@ -258,7 +241,7 @@ static void mf_launch_one(ma_ctx* ctx, unsigned grid, const float* flow, int H, 
 }
 
 template <int KIND>
-static void mf_launch(ma_ctx* ctx, bool generic, unsigned grid, const float* flow, int H, int W, const MfWeight& wt, int r,
+static void mf_launch(ma_ctx* ctx, bool generic, unsigned grid, const float* flow, int H, int W, const MaWeight& wt, int r,
                       int mode, float thresh, int nbx, float* out, unsigned char* keep, unsigned long long* counts)
 {
     static_assert(MF_REG_MAX_RADIUS == 3, "one case per radius of the register path");
@@ -278,12 +261,8 @@ extern "C" int ma_median_flow(ma_ctx* ctx, const float* flow, int H, int W, int 
     MA_REQUIRE(out != flow, "out and flow must be distinct arrays: a median reads its neighbours");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= MF_SIDE_MAX && W <= MF_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_REQUIRE(r >= 1 && r <= MA_MEDIAN_MAX_RADIUS, "r must be in [1, 7]");
-    MA_REQUIRE(weight_kind >= MA_SMOOTH_WEIGHT_NONE && weight_kind <= MA_SMOOTH_WEIGHT_CELLS, "unknown weight kind");
+    MA_TRY(ma_weight_check(weight, weight_kind, true, {out, keep}, cell_h, cell_w));
     MA_REQUIRE(mode == MA_MEDIAN_ALL || mode == MA_MEDIAN_OUTLIERS, "unknown mode");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight, "NULL weight");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || (weight != (const void*)out && weight != (const void*)keep),
-               "weight must be neither out nor keep");
-    MA_REQUIRE(weight_kind != MA_SMOOTH_WEIGHT_CELLS || (cell_h >= 1 && cell_w >= 1), "cell size must be >= 1");
     MA_REQUIRE(thresh >= 0.f, "thresh must not be NaN or negative");
     MA_REQUIRE((flags & ~MA_MEDIAN_GENERIC) == 0, "unknown flags");
     const long long nbx = (W + MF_TW - 1) / MF_TW, nby = (H + MF_TH - 1) / MF_TH;
@@ -296,16 +275,12 @@ extern "C" int ma_median_flow(ma_ctx* ctx, const float* flow, int H, int W, int 
         counts = (unsigned long long*)ctx->ws;
         MA_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), ctx->stream));
     }
-    MfWeight wt{weight, 1, 1, 1};
-    if (weight_kind == MA_SMOOTH_WEIGHT_CELLS) wt = MfWeight{weight, cell_h, cell_w, (int)(((long long)W + cell_w - 1) / cell_w)};
+    const MaWeight wt = ma_weight_map(weight, weight_kind, W, cell_h, cell_w);
     const bool generic = (flags & MA_MEDIAN_GENERIC) != 0 || r > MF_REG_MAX_RADIUS;
     const unsigned grid = (unsigned)(nbx * nby);
-    switch (weight_kind) {
-    case MA_SMOOTH_WEIGHT_F32: mf_launch<MA_SMOOTH_WEIGHT_F32>(ctx, generic, grid, flow, H, W, wt, r, mode, thresh, (int)nbx, out, keep, counts); break;
-    case MA_SMOOTH_WEIGHT_U8: mf_launch<MA_SMOOTH_WEIGHT_U8>(ctx, generic, grid, flow, H, W, wt, r, mode, thresh, (int)nbx, out, keep, counts); break;
-    case MA_SMOOTH_WEIGHT_CELLS: mf_launch<MA_SMOOTH_WEIGHT_CELLS>(ctx, generic, grid, flow, H, W, wt, r, mode, thresh, (int)nbx, out, keep, counts); break;
-    default: mf_launch<MA_SMOOTH_WEIGHT_NONE>(ctx, generic, grid, flow, H, W, wt, r, mode, thresh, (int)nbx, out, keep, counts); break;
-    }
+    ma_weight_dispatch(weight_kind, [&](auto kind) {
+        mf_launch<kind()>(ctx, generic, grid, flow, H, W, wt, r, mode, thresh, (int)nbx, out, keep, counts);
+    });
     MA_HIP(hipGetLastError());
     if (counts_host) {
         MA_HIP(hipMemcpyAsync(ctx->pinned, counts, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));

@@ -12,6 +12,7 @@
 //     integer atomic per wave and statistic.
 // LDS is sized by r at launch (40 KiB at r = 12, 97 KiB at r = 128).
 #include "../../include/microaligner_flowrefine.h"
+#include "weight_map.h"
 #include "window_fir.h"
 
 #include <cmath>
@@ -22,21 +23,17 @@ constexpr int FR_SIDE_MAX = 1 << 24;
 constexpr int FR_PLANES = 5;
 static_assert(MA_REFINE_MAX_RADIUS == WF_MAX_RADIUS, "the tile of window_fir.h is sized for this radius");
 
-__device__ __forceinline__ bool fr_finite(float v) { return fabsf(v) < INFINITY; }
-
 // plane P of the header at (x, y), which must lie inside the image: every read is clamped into it
 template <int P, typename T>
 __device__ __forceinline__ float fr_product(const T* __restrict__ ref, const float* __restrict__ wp, const void* __restrict__ weight,
                                             int kind, int H, int W, int x, int y)
 {
     const size_t row = (size_t)y * W, i = row + x;
-    float w = 1.f;
-    if (kind == MA_SMOOTH_WEIGHT_F32) w = ((const float*)weight)[i];                          // wave-uniform branches
-    else if (kind == MA_SMOOTH_WEIGHT_U8) w = ((const unsigned char*)weight)[i] ? 1.f : 0.f;
+    const float w = d_weight_px(weight, kind, i);
     const float c = wp[i], rv = (float)ref[i];
     const float gx = 0.5f * (wp[row + min(x + 1, W - 1)] - wp[row + max(x - 1, 0)]);
     const float gy = 0.5f * (wp[(size_t)min(y + 1, H - 1) * W + x] - wp[(size_t)max(y - 1, 0) * W + x]);
-    if (!(w > 0.f && w < INFINITY && fr_finite(c) && fr_finite(rv) && fr_finite(gx) && fr_finite(gy))) return 0.f;
+    if (!(d_weight_counts(w) && d_finite(c) && d_finite(rv) && d_finite(gx) && d_finite(gy))) return 0.f;
     const float a = w * gx, b = w * gy;
     if (P == 0) return a * gx;
     if (P == 1) return a * gy;
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(64 * WF_NW) void fr_col_kernel(const float* __restr
         const float a = S[0][q] + floor, c = S[2][q] + floor;
         const float det = a * c - sxy * sxy;
         float dx = __fdiv_rn(c * sxe - sxy * sye, det), dy = __fdiv_rn(a * sye - sxy * sxe, det);
-        if (!(det > 0.f && det < INFINITY && fr_finite(dx) && fr_finite(dy))) {
+        if (!(det > 0.f && det < INFINITY && d_finite(dx) && d_finite(dy))) {
             dx = dy = 0.f;
             invalid++;
         }
@@ -161,11 +158,8 @@ extern "C" int ma_flow_refine_step(ma_ctx* ctx, const void* ref, int dtype, cons
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FR_SIDE_MAX && W <= FR_SIDE_MAX, "image sides must be in [1, 2^24]");
     MA_REQUIRE(r >= 1 && r <= MA_REFINE_MAX_RADIUS, "r must be in [1, 128]");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "unknown dtype");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight_kind == MA_SMOOTH_WEIGHT_F32 || weight_kind == MA_SMOOTH_WEIGHT_U8,
-               "the weight must be none or per pixel, float32 or uint8");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight, "NULL weight");
+    MA_TRY(ma_weight_check(weight, weight_kind, false, {out}, 1, 1));
     MA_REQUIRE(ref != (const void*)out && (const void*)warped != (const void*)out, "ref, warped and out must be distinct arrays");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight != (const void*)out, "weight and out must be distinct arrays");
     MA_REQUIRE(std::isfinite(floor) && floor > 0.f, "floor must be finite and positive");
     MA_REQUIRE(std::isfinite(max_step) && max_step > 0.f, "max_step must be finite and positive");
     WfTaps taps;
@@ -173,24 +167,16 @@ extern "C" int ma_flow_refine_step(ma_ctx* ctx, const void* ref, int dtype, cons
     MA_HIP(hipSetDevice(ctx->device));
     unsigned long long* stats;
     MA_TRY(wf_counters(ctx, stats_host != nullptr, MA_REFINE_STATS, &stats));
-    float* aux = (float*)ma_pool_alloc(ctx, WF_TAPS * sizeof(float));
-    if (!aux) return MA_ENOMEM;
-    float* ws = (float*)ma_pool_alloc(ctx, (size_t)H * W * FR_PLANES * sizeof(float));
-    if (!ws) {
-        ma_pool_free(ctx, aux);
-        return MA_ENOMEM;
-    }
-    hipLaunchKernelGGL(wf_setup_kernel<>, dim3(1), dim3(256), 0, ctx->stream, taps, r, aux);
+    WfBuffers b;
+    MA_TRY(wf_acquire(ctx, 0, FR_PLANES, H, W, 0, &b));
+    hipLaunchKernelGGL(wf_setup_kernel<>, dim3(1), dim3(256), 0, ctx->stream, taps, r, b.aux);
     int rc;
     switch (dtype) {
-    case MA_U8: rc = fr_launch<unsigned char>(ctx, ref, warped, weight, weight_kind, H, W, r, aux, ws, floor, max_step, flow, out, stats); break;
-    case MA_U16: rc = fr_launch<unsigned short>(ctx, ref, warped, weight, weight_kind, H, W, r, aux, ws, floor, max_step, flow, out, stats); break;
-    default: rc = fr_launch<float>(ctx, ref, warped, weight, weight_kind, H, W, r, aux, ws, floor, max_step, flow, out, stats); break;
+    case MA_U8: rc = fr_launch<unsigned char>(ctx, ref, warped, weight, weight_kind, H, W, r, b.aux, b.ws, floor, max_step, flow, out, stats); break;
+    case MA_U16: rc = fr_launch<unsigned short>(ctx, ref, warped, weight, weight_kind, H, W, r, b.aux, b.ws, floor, max_step, flow, out, stats); break;
+    default: rc = fr_launch<float>(ctx, ref, warped, weight, weight_kind, H, W, r, b.aux, b.ws, floor, max_step, flow, out, stats); break;
     }
-    // stream-ordered reuse: the next call on this ctx that takes the buffers runs behind these kernels
-    ma_pool_free(ctx, ws);
-    ma_pool_free(ctx, aux);
-    MA_TRY(rc);
+    MA_TRY(wf_finish(ctx, b, rc, nullptr));
     if (stats_host) MA_TRY(wf_read_counters(ctx, stats, MA_REFINE_STATS, stats_host));
     return MA_OK;
 }

@@ -9,6 +9,7 @@
 #include "../../include/microaligner_flowsmooth.h"
 #include "cell_grid.h"
 #include "flow_jacobian.h"
+#include "weight_map.h"
 #include "window_fir.h"
 
 #include <cmath>
@@ -19,27 +20,10 @@ namespace {
 constexpr int FS_SIDE_MAX = 1 << 24;
 static_assert(MA_SMOOTH_MAX_RADIUS == WF_MAX_RADIUS, "the tile of window_fir.h is sized for this radius");
 
-struct FsWeight {
-    const void* p;
-    int ch, cw, gx;
-};
-
-__device__ __forceinline__ bool fs_finite(float v) { return fabsf(v) < INFINITY; }
-
-// weight(p) of the header; i = y * W + x
-template <int KIND>
-__device__ __forceinline__ float fs_weight_at(const FsWeight& wt, size_t i, int x, int y)
-{
-    if (KIND == MA_SMOOTH_WEIGHT_F32) return ((const float*)wt.p)[i];
-    if (KIND == MA_SMOOTH_WEIGHT_U8) return ((const unsigned char*)wt.p)[i] ? 1.f : 0.f;
-    if (KIND == MA_SMOOTH_WEIGHT_CELLS) return ((const float*)wt.p)[(size_t)(y / wt.ch) * wt.gx + x / wt.cw];
-    return 1.f;
-}
-
 // the effective weight w(p) of the header
 __device__ __forceinline__ float fs_effective(float wgt, float2 f)
 {
-    return (wgt > 0.f && wgt < INFINITY && fs_finite(f.x) && fs_finite(f.y)) ? wgt : 0.f;
+    return (d_weight_counts(wgt) && d_finite(f.x) && d_finite(f.y)) ? wgt : 0.f;
 }
 
 // the header's rule on an axis of n ones at position x: the samples inside the image are 1, the others 0
@@ -65,7 +49,7 @@ __global__ __launch_bounds__(256) void fs_setup_kernel(WfTaps taps, int r, int W
 
 // Row pass.  Block: rows [y0, y0 + 64) x output columns [x0, x0 + WF_S); lane = row.  ws: the three (W, H) planes.
 template <int KIND>
-__global__ __launch_bounds__(64 * WF_NW) void fs_row_kernel(const float2* __restrict__ flow, int H, int W, FsWeight wt, int r,
+__global__ __launch_bounds__(64 * WF_NW) void fs_row_kernel(const float2* __restrict__ flow, int H, int W, MaWeight wt, int r,
                                                             const float* __restrict__ taps, int nbx, float* __restrict__ ws)
 {
     extern __shared__ float lds[];   // [64][pitch]
@@ -84,7 +68,7 @@ __global__ __launch_bounds__(64 * WF_NW) void fs_row_kernel(const float2* __rest
                 if (y < H && x >= 0 && x < W) {
                     const size_t i = (size_t)y * W + x;
                     const float2 f = flow[i];
-                    const float w = fs_effective(fs_weight_at<KIND>(wt, i, x, y), f);
+                    const float w = fs_effective(d_weight_at<KIND>(wt, i, x, y), f);
                     val = p == 2 ? w : (w > 0.f ? w * (p == 0 ? f.x : f.y) : 0.f);
                 }
                 line[c] = val;
@@ -108,7 +92,7 @@ __global__ __launch_bounds__(64 * WF_NW) void fs_row_kernel(const float2* __rest
 // flow and out may be one array: neither is __restrict__, and a thread reads flow only at the pixel it writes.
 template <int KIND, int MODE>
 __global__ __launch_bounds__(64 * WF_NW) void fs_col_kernel(const float* __restrict__ ws, int H, int W, const float2* flow,
-                                                            FsWeight wt, int r, const float* __restrict__ aux, int nbx,
+                                                            MaWeight wt, int r, const float* __restrict__ aux, int nbx,
                                                             float min_support, float2* out,
                                                             unsigned long long* __restrict__ unsupported)
 {
@@ -148,7 +132,7 @@ __global__ __launch_bounds__(64 * WF_NW) void fs_col_kernel(const float* __restr
         else missed++;
         if (MODE == MA_SMOOTH_BLEND) {
             const float2 f = flow[i];
-            const float w = fs_effective(fs_weight_at<KIND>(wt, i, x, y), f);
+            const float w = fs_effective(d_weight_at<KIND>(wt, i, x, y), f);
             if (w > 0.f) {
                 const float sn = aux[WF_TAPS + W + y] * rs;
                 const float c = __fdiv_rn(s2, sn);
@@ -181,7 +165,7 @@ __global__ __launch_bounds__(256) void fs_bad_kernel(const float2* __restrict__ 
         const float2 f = flow[i];
         const double det = ma_flow_det_j([&](int dx, int dy) { return flow[(size_t)(y + dy) * W + (x + dx)]; }, x, y, W, H);
         folded = ma_finite(det) && det <= 0.0;
-        invalid = !(fs_finite(f.x) && fs_finite(f.y));
+        invalid = !(d_finite(f.x) && d_finite(f.y));
         bad[i] = (folded | invalid) ? 1 : 0;
     }
 #pragma unroll
@@ -235,7 +219,7 @@ __global__ __launch_bounds__(256) void fs_dilate_kernel(const unsigned char* __r
 }
 
 template <int KIND>
-static int fs_launch(ma_ctx* ctx, const float* flow, int H, int W, const FsWeight& wt, int r, int mode, float min_support,
+static int fs_launch(ma_ctx* ctx, const float* flow, int H, int W, const MaWeight& wt, int r, int mode, float min_support,
                      const float* aux, float* ws, float* out, unsigned long long* counter)
 {
     const void* col = mode == MA_SMOOTH_BLEND ? reinterpret_cast<const void*>(fs_col_kernel<KIND, MA_SMOOTH_BLEND>)
@@ -263,11 +247,8 @@ extern "C" int ma_smooth_flow(ma_ctx* ctx, const float* flow, int H, int W, cons
     MA_REQUIRE(ctx && flow && taps_host && out, "NULL argument");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FS_SIDE_MAX && W <= FS_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_REQUIRE(r >= 1 && r <= MA_SMOOTH_MAX_RADIUS, "r must be in [1, 128]");
-    MA_REQUIRE(weight_kind >= MA_SMOOTH_WEIGHT_NONE && weight_kind <= MA_SMOOTH_WEIGHT_CELLS, "unknown weight kind");
+    MA_TRY(ma_weight_check(weight, weight_kind, true, {out}, cell_h, cell_w));
     MA_REQUIRE(mode == MA_SMOOTH_ALL || mode == MA_SMOOTH_BLEND, "unknown mode");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight, "NULL weight");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight != (const void*)out, "weight and out must be distinct arrays");
-    MA_REQUIRE(weight_kind != MA_SMOOTH_WEIGHT_CELLS || (cell_h >= 1 && cell_w >= 1), "cell size must be >= 1");
     MA_REQUIRE(std::isfinite(min_support) && min_support >= 0.f, "min_support must be finite and not negative");
     WfTaps taps;
     MA_TRY(wf_taps(taps_host, r, &taps));
@@ -275,28 +256,16 @@ extern "C" int ma_smooth_flow(ma_ctx* ctx, const float* flow, int H, int W, cons
     unsigned long long* counter;
     MA_TRY(wf_counters(ctx, unsupported_host != nullptr, 1, &counter));
     const int ones = mode == MA_SMOOTH_BLEND ? 1 : 0;
-    const size_t aux_n = (size_t)WF_TAPS + (ones ? (size_t)W + H : 0);
-    float* aux = (float*)ma_pool_alloc(ctx, aux_n * sizeof(float));
-    if (!aux) return MA_ENOMEM;
-    float* ws = (float*)ma_pool_alloc(ctx, (size_t)H * W * 3 * sizeof(float));
-    if (!ws) {
-        ma_pool_free(ctx, aux);
-        return MA_ENOMEM;
-    }
-    FsWeight wt{weight, 1, 1, 1};
-    if (weight_kind == MA_SMOOTH_WEIGHT_CELLS) wt = FsWeight{weight, cell_h, cell_w, (int)(((long long)W + cell_w - 1) / cell_w)};
-    hipLaunchKernelGGL(fs_setup_kernel, dim3((unsigned)((aux_n + 255) / 256)), dim3(256), 0, ctx->stream, taps, r, W, H, ones, aux);
-    int rc;
-    switch (weight_kind) {
-    case MA_SMOOTH_WEIGHT_F32: rc = fs_launch<MA_SMOOTH_WEIGHT_F32>(ctx, flow, H, W, wt, r, mode, min_support, aux, ws, out, counter); break;
-    case MA_SMOOTH_WEIGHT_U8: rc = fs_launch<MA_SMOOTH_WEIGHT_U8>(ctx, flow, H, W, wt, r, mode, min_support, aux, ws, out, counter); break;
-    case MA_SMOOTH_WEIGHT_CELLS: rc = fs_launch<MA_SMOOTH_WEIGHT_CELLS>(ctx, flow, H, W, wt, r, mode, min_support, aux, ws, out, counter); break;
-    default: rc = fs_launch<MA_SMOOTH_WEIGHT_NONE>(ctx, flow, H, W, wt, r, mode, min_support, aux, ws, out, counter); break;
-    }
-    // stream-ordered reuse: the next call on this ctx that takes the buffers runs behind these kernels
-    ma_pool_free(ctx, ws);
-    ma_pool_free(ctx, aux);
-    MA_TRY(rc);
+    const size_t tail = ones ? (size_t)W + H : 0;
+    WfBuffers b;
+    MA_TRY(wf_acquire(ctx, tail, 3, H, W, 0, &b));
+    const MaWeight wt = ma_weight_map(weight, weight_kind, W, cell_h, cell_w);
+    hipLaunchKernelGGL(fs_setup_kernel, dim3((unsigned)((WF_TAPS + tail + 255) / 256)), dim3(256), 0, ctx->stream, taps, r, W, H,
+                       ones, b.aux);
+    const int rc = ma_weight_dispatch(weight_kind, [&](auto kind) {
+        return fs_launch<kind()>(ctx, flow, H, W, wt, r, mode, min_support, b.aux, b.ws, out, counter);
+    });
+    MA_TRY(wf_finish(ctx, b, rc, nullptr));
     if (unsupported_host) MA_TRY(wf_read_counters(ctx, counter, 1, unsupported_host));
     return MA_OK;
 }

@@ -13,6 +13,7 @@
 // LDS is sized by r at launch (40 KiB at r = 12, 97 KiB at r = 128).
 #include "../../include/microaligner_localcorr.h"
 #include "cell_grid.h"
+#include "weight_map.h"
 #include "window_fir.h"
 
 #include <cmath>
@@ -40,18 +41,14 @@ struct LcOut {
     int ch, cw, gx;
 };
 
-__device__ __forceinline__ bool lc_finite(float v) { return fabsf(v) < INFINITY; }
-
 // plane P of the header at (x, y), which must lie inside the image
 template <int P, typename T>
 __device__ __forceinline__ float lc_product(const T* __restrict__ ref, const LcIn& in, int W, int x, int y)
 {
     const size_t i = (size_t)y * W + x;
-    float w = 1.f;
-    if (in.kind == MA_SMOOTH_WEIGHT_F32) w = ((const float*)in.weight)[i];                          // wave-uniform branches
-    else if (in.kind == MA_SMOOTH_WEIGHT_U8) w = ((const unsigned char*)in.weight)[i] ? 1.f : 0.f;
+    const float w = d_weight_px(in.weight, in.kind, i);
     const float a = (float)ref[i] - in.center_ref, b = in.img[i] - in.center_img;
-    if (!(w > 0.f && w < INFINITY && lc_finite(a) && lc_finite(b))) return 0.f;
+    if (!(w > 0.f && w < INFINITY && d_finite(a) && d_finite(b))) return 0.f;   // d_weight_counts() compiles to other code here
     if (P == 0) return w;
     const float wa = w * a, wb = w * b;
     if (P == 1) return wa;
@@ -204,9 +201,7 @@ extern "C" int ma_local_correlation(ma_ctx* ctx, const void* ref, int dtype, con
     MA_REQUIRE(H >= 1 && W >= 1 && H <= LC_SIDE_MAX && W <= LC_SIDE_MAX, "image sides must be in [1, 2^24]");
     MA_REQUIRE(r >= 1 && r <= MA_LOCALCORR_MAX_RADIUS, "r must be in [1, 128]");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "unknown dtype");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight_kind == MA_SMOOTH_WEIGHT_F32 || weight_kind == MA_SMOOTH_WEIGHT_U8,
-               "the weight must be none or per pixel, float32 or uint8");
-    MA_REQUIRE(weight_kind == MA_SMOOTH_WEIGHT_NONE || weight, "NULL weight");
+    MA_TRY(ma_weight_check(weight, weight_kind, false, {}, 1, 1));   // as before, the outputs are not compared with it
     MA_REQUIRE(std::isfinite(center_ref) && std::isfinite(center_img), "the centres must be finite");
     MA_REQUIRE(std::isfinite(floor) && floor > 0.f, "floor must be finite and positive");
     MA_REQUIRE(std::isfinite(min_support) && min_support >= 0.f, "min_support must be finite and not negative");
@@ -216,55 +211,17 @@ extern "C" int ma_local_correlation(ma_ctx* ctx, const void* ref, int dtype, con
     const LcIn in{img, weight, weight_kind, center_ref, center_img};
     LcOut o{score, weight_out, nullptr, floor, min_support, lo, hi, hi - lo, 1, 1, 1};
     long long ncells = 0;
-    if (counts_host) {
-        MaCellGrid g;
-        MA_TRY(ma_cell_grid(H, W, cell_h, cell_w, &g, &ncells));
-        o.ch = g.ch;
-        o.cw = g.cw;
-        o.gx = g.gx;
-    }
+    if (counts_host) MA_TRY(ma_cell_counts_grid(H, W, cell_h, cell_w, &o, &ncells));
     MA_HIP(hipSetDevice(ctx->device));
-    const size_t counts_bytes = (size_t)ncells * MA_LOCALCORR_CLASSES * sizeof(unsigned long long);
-    float* aux = (float*)ma_pool_alloc(ctx, WF_TAPS * sizeof(float));
-    if (!aux) return MA_ENOMEM;
-    float* ws = (float*)ma_pool_alloc(ctx, (size_t)H * W * LC_PLANES * sizeof(float));
-    if (!ws) {
-        ma_pool_free(ctx, aux);
-        return MA_ENOMEM;
+    WfBuffers b;
+    MA_TRY(wf_acquire(ctx, 0, LC_PLANES, H, W, (size_t)ncells * MA_LOCALCORR_CLASSES, &b));
+    o.counts = b.counts;
+    hipLaunchKernelGGL(wf_setup_kernel<>, dim3(1), dim3(256), 0, ctx->stream, taps, r, b.aux);
+    int rc;
+    switch (dtype) {
+    case MA_U8: rc = lc_launch<unsigned char>(ctx, ref, in, H, W, r, b.aux, b.ws, o); break;
+    case MA_U16: rc = lc_launch<unsigned short>(ctx, ref, in, H, W, r, b.aux, b.ws, o); break;
+    default: rc = lc_launch<float>(ctx, ref, in, H, W, r, b.aux, b.ws, o); break;
     }
-    if (counts_host) {
-        o.counts = (unsigned long long*)ma_pool_alloc(ctx, counts_bytes);
-        if (!o.counts) {
-            ma_pool_free(ctx, ws);
-            ma_pool_free(ctx, aux);
-            return MA_ENOMEM;
-        }
-    }
-    int rc = MA_OK;
-    if (o.counts && hipMemsetAsync(o.counts, 0, counts_bytes, ctx->stream) != hipSuccess) {
-        ma_set_error("hipMemsetAsync of the class counts failed");
-        rc = MA_EHIP;
-    }
-    if (rc == MA_OK) {
-        hipLaunchKernelGGL(wf_setup_kernel<>, dim3(1), dim3(256), 0, ctx->stream, taps, r, aux);
-        switch (dtype) {
-        case MA_U8: rc = lc_launch<unsigned char>(ctx, ref, in, H, W, r, aux, ws, o); break;
-        case MA_U16: rc = lc_launch<unsigned short>(ctx, ref, in, H, W, r, aux, ws, o); break;
-        default: rc = lc_launch<float>(ctx, ref, in, H, W, r, aux, ws, o); break;
-        }
-    }
-    if (rc == MA_OK && o.counts) {
-        // the counts go straight into the caller's array: unsigned on the device, the same bits as the long long asked for
-        hipError_t e = hipMemcpyAsync(counts_host, o.counts, counts_bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            ma_set_error("reading the class counts failed: %s", hipGetErrorString(e));
-            rc = MA_EHIP;
-        }
-    }
-    // stream-ordered reuse: the next call on this ctx that takes the buffers runs behind these kernels
-    if (o.counts) ma_pool_free(ctx, o.counts);
-    ma_pool_free(ctx, ws);
-    ma_pool_free(ctx, aux);
-    return rc;
+    return wf_finish(ctx, b, rc, counts_host);
 }

@@ -175,55 +175,17 @@ extern "C" int ma_texture_maps(ma_ctx* ctx, const void* img, int dtype, int H, i
         o.floor = floor;
     }
     long long ncells = 0;
-    if (counts_host) {
-        MaCellGrid g;
-        MA_TRY(ma_cell_grid(H, W, cell_h, cell_w, &g, &ncells));
-        o.ch = g.ch;
-        o.cw = g.cw;
-        o.gx = g.gx;
-    }
+    if (counts_host) MA_TRY(ma_cell_counts_grid(H, W, cell_h, cell_w, &o, &ncells));
     MA_HIP(hipSetDevice(ctx->device));
-    const size_t counts_bytes = (size_t)ncells * MA_TEXTURE_CLASSES * sizeof(unsigned long long);
-    float* aux = (float*)ma_pool_alloc(ctx, WF_TAPS * sizeof(float));
-    if (!aux) return MA_ENOMEM;
-    float* ws = (float*)ma_pool_alloc(ctx, (size_t)H * W * 3 * sizeof(float));
-    if (!ws) {
-        ma_pool_free(ctx, aux);
-        return MA_ENOMEM;
+    WfBuffers b;
+    MA_TRY(wf_acquire(ctx, 0, 3, H, W, (size_t)ncells * MA_TEXTURE_CLASSES, &b));
+    o.counts = b.counts;
+    hipLaunchKernelGGL(wf_setup_kernel<>, dim3(1), dim3(256), 0, ctx->stream, taps, r, b.aux);
+    int rc;
+    switch (dtype) {
+    case MA_U8: rc = tx_launch<unsigned char>(ctx, img, H, W, r, b.aux, b.ws, o); break;
+    case MA_U16: rc = tx_launch<unsigned short>(ctx, img, H, W, r, b.aux, b.ws, o); break;
+    default: rc = tx_launch<float>(ctx, img, H, W, r, b.aux, b.ws, o); break;
     }
-    if (counts_host) {
-        o.counts = (unsigned long long*)ma_pool_alloc(ctx, counts_bytes);
-        if (!o.counts) {
-            ma_pool_free(ctx, ws);
-            ma_pool_free(ctx, aux);
-            return MA_ENOMEM;
-        }
-    }
-    int rc = MA_OK;
-    if (o.counts && hipMemsetAsync(o.counts, 0, counts_bytes, ctx->stream) != hipSuccess) {
-        ma_set_error("hipMemsetAsync of the class counts failed");
-        rc = MA_EHIP;
-    }
-    if (rc == MA_OK) {
-        hipLaunchKernelGGL(wf_setup_kernel<>, dim3(1), dim3(256), 0, ctx->stream, taps, r, aux);
-        switch (dtype) {
-        case MA_U8: rc = tx_launch<unsigned char>(ctx, img, H, W, r, aux, ws, o); break;
-        case MA_U16: rc = tx_launch<unsigned short>(ctx, img, H, W, r, aux, ws, o); break;
-        default: rc = tx_launch<float>(ctx, img, H, W, r, aux, ws, o); break;
-        }
-    }
-    if (rc == MA_OK && o.counts) {
-        // the counts go straight into the caller's array: unsigned on the device, the same bits as the long long asked for
-        hipError_t e = hipMemcpyAsync(counts_host, o.counts, counts_bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            ma_set_error("reading the class counts failed: %s", hipGetErrorString(e));
-            rc = MA_EHIP;
-        }
-    }
-    // stream-ordered reuse: the next call on this ctx that takes the buffers runs behind these kernels
-    if (o.counts) ma_pool_free(ctx, o.counts);
-    ma_pool_free(ctx, ws);
-    ma_pool_free(ctx, aux);
-    return rc;
+    return wf_finish(ctx, b, rc, counts_host);
 }

@@ -14,8 +14,12 @@
 //   - output: lane = line, and a line of the input is a column of the output, so the stores are coalesced as well: the row
 //     pass writes its planes transposed, the column pass ends in the user's own epilogue and writes row-major.
 // What is stated here: the tile's constants, the tap table and its setup, one plane of a row pass (wf_row_plane) and the host
-// side of a call.  The column kernels, and the row kernel of the flow smoothing, stage and filter in their own bodies, in the
-// words of wf_row_plane: they were compiled as one body, and taken out into a function they compile to other code.
+// side of a call: the tap check, the shape of the launches, the counters of the ctx workspace, and the pool buffers of a call
+// with their unwinding and the read-back of per-cell counts (wf_acquire, wf_finish).  The weight that three of the users
+// take is weight_map.h.  The column kernels, and the row kernel of the flow smoothing, stage and filter in their own bodies,
+// in the words of wf_row_plane: they were compiled as one body, and taken out into a function they compile to other code.
+// So does the per-cell class counter of tx_col_kernel and lc_col_kernel (the `while (todo)` loop with the ballots): as one
+// templated function it changed 1395 of the 12552 lines of texture.hip's device assembly and 4602 of local_correlation.hip's.
 // One kernel family for every r in 1 .. 128: LDS is sized by r at launch (40 KiB at r = 12, 97 KiB at r = 128).
 // Bound by the instructions it issues (two LDS reads and three packed operations per tap and 16 outputs), like the window
 // blurs, not by bytes; at large r the halo (2r staged elements beside 128 outputs per line) adds to it.
@@ -146,6 +150,49 @@ inline int wf_read_counters(ma_ctx* ctx, const unsigned long long* counter, int 
     MA_HIP(hipMemcpyAsync(ctx->pinned, counter, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     MA_HIP(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < n; k++) host[k] = (long long)((const unsigned long long*)ctx->pinned)[k];
+    return MA_OK;
+}
+
+// The pool buffers of a call: aux (the tap table and `tail` floats behind it), the workspace of `planes` (W, H) planes and,
+// for the maps with per-cell class counts, n zeroed counters (n = 0: none).
+struct WfBuffers {
+    float* aux;
+    float* ws;
+    unsigned long long* counts;
+    size_t n;
+};
+
+// Ends a call: with rc == MA_OK and counters, reads them straight into the caller's array (unsigned on the device, the same
+// bits as the long long asked for) and synchronises; then frees in the order counts, ws, aux.  -> the first error.
+// Stream-ordered reuse: the next call on this ctx that takes the buffers runs behind the kernels launched here.
+inline int wf_finish(ma_ctx* ctx, const WfBuffers& b, int rc, long long* counts_host)
+{
+    if (rc == MA_OK && b.counts) {
+        hipError_t e = hipMemcpyAsync(counts_host, b.counts, b.n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            ma_set_error("reading the class counts failed: %s", hipGetErrorString(e));
+            rc = MA_EHIP;
+        }
+    }
+    if (b.counts) ma_pool_free(ctx, b.counts);
+    if (b.ws) ma_pool_free(ctx, b.ws);
+    if (b.aux) ma_pool_free(ctx, b.aux);
+    return rc;
+}
+
+// Takes the buffers, the memset of the counters first on the stream; on failure frees what it took.
+inline int wf_acquire(ma_ctx* ctx, size_t tail, int planes, int H, int W, size_t n, WfBuffers* b)
+{
+    *b = WfBuffers{nullptr, nullptr, nullptr, n};
+    b->aux = (float*)ma_pool_alloc(ctx, ((size_t)WF_TAPS + tail) * sizeof(float));
+    if (b->aux) b->ws = (float*)ma_pool_alloc(ctx, (size_t)H * W * planes * sizeof(float));
+    if (b->ws && n) b->counts = (unsigned long long*)ma_pool_alloc(ctx, n * sizeof(unsigned long long));
+    if (!b->ws || (n && !b->counts)) return wf_finish(ctx, *b, MA_ENOMEM, nullptr);
+    if (n && hipMemsetAsync(b->counts, 0, n * sizeof(unsigned long long), ctx->stream) != hipSuccess) {
+        ma_set_error("hipMemsetAsync of the class counts failed");
+        return wf_finish(ctx, *b, MA_EHIP, nullptr);
+    }
     return MA_OK;
 }
 

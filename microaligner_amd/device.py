@@ -139,6 +139,38 @@ def _real(v, name):
     return float(v)
 
 
+def _finite_f32(v, name):
+    x = _real(v, name)
+    with np.errstate(over="ignore"):
+        x = np.float32(x)
+    if not np.isfinite(x):
+        raise ValueError(f"{name} must be finite as float32, got {v!r}")
+    return float(x)
+
+
+def _positive_f32(v, name):
+    x = _finite_f32(v, name)
+    if not x > 0:
+        raise ValueError(f"{name} must be finite and positive as float32, got {v!r}")
+    return x
+
+
+def _matrix_2x3(m, name):
+    """a finite 2 x 3 matrix as 6 float64 in row order"""
+    try:
+        t = np.array(m, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a 2 x 3 matrix") from None
+    if t.shape != (2, 3) or not np.all(np.isfinite(t)):
+        raise ValueError(f"{name} must be a finite 2 x 3 matrix")
+    return np.ascontiguousarray(t).ravel()
+
+
+def _image_sides(H, W):
+    if not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
+        raise ValueError(f"image sides must be in [1, 2^24], got {(H, W)}")
+
+
 def _check_taps(taps):
     if not isinstance(taps, np.ndarray) or taps.dtype != np.float32 or taps.ndim != 1:
         raise ValueError("taps must be a 1-D float32 numpy array t[0 .. r]")
@@ -177,27 +209,48 @@ def _cell_size_hw(cell_size):
     return int(ch), int(cw)
 
 
-def _weight_kind(weight, cell_size, H, W):
-    """(kind, cell_h, cell_w) of a smooth_flow-style weight: None; an (H, W) float32 or uint8 array (numpy or device); or,
-    with cell_size, a (gy, gx) float32 map on that cell grid."""
+def _weight_kind(weight, H, W, cell_size=None, cells=None):
+    """(kind, cell_h, cell_w) of a weight argument: None, or an (H, W) float32 or uint8 array (numpy or device), or a per-cell
+    map as far as `cells` says the call takes one:
+      None    never (direct_affine_moments, flow_refine_step, local_correlation); cell_size is not theirs to pass;
+      "map"   with cell_size a (gy, gx) float32 map on that cell grid and nothing else; cell_size has no meaning without
+              one (smooth_flow, median_flow);
+      "grid"  cell_size is the grid of the call whatever the weight, None standing for one cell, and the weight is per
+              pixel or a float32 map of the grid's shape (flow_affine_moments).
+    cell_h, cell_w: the cells, (H, W) for the one cell of "grid", else (1, 1)."""
+    ch, cw = (H, W) if cells == "grid" else (1, 1)
+    if cell_size is not None:
+        ch, cw = _cell_size_hw(cell_size)
+    grid = (-(-H // ch), -(-W // cw))
+    only_cells = cells == "map" and cell_size is not None
     if weight is None:
-        if cell_size is not None:
+        if only_cells:
             raise ValueError("cell_size only has a meaning together with a per-cell weight")
-        return L.MA_SMOOTH_WEIGHT_NONE, 1, 1
+        return L.MA_SMOOTH_WEIGHT_NONE, ch, cw
     if not isinstance(weight, (np.ndarray, DeviceArray)):
         raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
     wshape, wdtype = tuple(weight.shape), weight.dtype
-    if cell_size is not None:
-        ch, cw = _cell_size_hw(cell_size)
-        want = (-(-H // ch), -(-W // cw))
-        if wdtype != np.float32 or wshape != want:
-            raise ValueError(f"a per-cell weight of cells {(ch, cw)} must be float32 of shape {want}, got {wdtype} {wshape}")
+    if not only_cells and wshape == (H, W) and wdtype == np.float32:
+        return L.MA_SMOOTH_WEIGHT_F32, ch, cw
+    if not only_cells and wshape == (H, W) and wdtype == np.uint8:
+        return L.MA_SMOOTH_WEIGHT_U8, ch, cw
+    if cell_size is not None and wshape == grid and wdtype == np.float32:
         return L.MA_SMOOTH_WEIGHT_CELLS, ch, cw
-    if wshape == (H, W) and wdtype == np.float32:
-        return L.MA_SMOOTH_WEIGHT_F32, 1, 1
-    if wshape == (H, W) and wdtype == np.uint8:
-        return L.MA_SMOOTH_WEIGHT_U8, 1, 1
-    raise ValueError(f"a per-pixel weight must be float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+    if only_cells:
+        raise ValueError(f"a per-cell weight of cells {(ch, cw)} must be float32 of shape {grid}, got {wdtype} {wshape}")
+    per_cell = f", or float32 of shape {grid} for cells {(ch, cw)}" if cell_size is not None else ""
+    raise ValueError(f"a per-pixel weight must be float32 or uint8 of shape {(H, W)}{per_cell}, got {wdtype} {wshape}")
+
+
+def _want_and_cells(want, planes, cell_size):
+    """(cell_h, cell_w or None twice, want as a tuple) of a call that makes the planes named in `want` and, with cell_size,
+    per-cell counts"""
+    if isinstance(want, str) or not all(isinstance(n, str) and n in planes for n in want) or \
+            len(set(want)) != len(tuple(want)):
+        raise ValueError(f"want must name distinct planes among {planes}, got {want!r}")
+    if not tuple(want) and cell_size is None:
+        raise ValueError("no output was asked for")
+    return ((None, None) if cell_size is None else _cell_size_hw(cell_size)) + (tuple(want),)
 
 
 def smooth_flow_params(flow, taps, weight=None, cell_size=None, where="all", min_support=0.0):
@@ -209,13 +262,11 @@ def smooth_flow_params(flow, taps, weight=None, cell_size=None, where="all", min
     taps, r = _check_taps(taps)
     if not isinstance(where, str) or where not in SMOOTH_MODES:
         raise ValueError(f"unknown mode {where!r}: expected one of {sorted(SMOOTH_MODES)}")
-    ms = _real(min_support, "min_support")
-    with np.errstate(over="ignore"):
-        ms = np.float32(ms)
-    if not (np.isfinite(ms) and ms >= 0):
-        raise ValueError(f"min_support must be finite and not negative as float32, got {min_support!r}")
-    kind, ch, cw = _weight_kind(weight, cell_size, H, W)
-    return H, W, taps, r, kind, ch, cw, SMOOTH_MODES[where], float(ms)
+    ms = _finite_f32(min_support, "min_support")
+    if not ms >= 0:
+        raise ValueError(f"min_support must not be negative, got {min_support!r}")
+    kind, ch, cw = _weight_kind(weight, H, W, cell_size, "map")
+    return H, W, taps, r, kind, ch, cw, SMOOTH_MODES[where], ms
 
 
 def fold_mask_params(flow, margin):
@@ -254,7 +305,7 @@ def median_flow_params(flow, radius=2, weight=None, cell_size=None, where="all",
             raise ValueError(f"thresh must not be NaN or negative, got {thresh!r}")
     if not isinstance(generic, (bool, np.bool_)):
         raise ValueError(f"generic must be a bool, got {generic!r}")
-    kind, ch, cw = _weight_kind(weight, cell_size, H, W)
+    kind, ch, cw = _weight_kind(weight, H, W, cell_size, "map")
     return H, W, int(radius), kind, ch, cw, MEDIAN_MODES[where], float(th), L.MA_MEDIAN_GENERIC if generic else 0
 
 
@@ -274,25 +325,13 @@ def texture_maps_params(img, taps, floor=None, cell_size=None, want=("lam_min", 
         raise ValueError(f"expected a 2D grayscale image, got shape {tuple(img.shape)}")
     dtype = _dt(img.dtype)
     H, W = (int(v) for v in img.shape)
-    if not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
-        raise ValueError(f"image sides must be in [1, 2^24], got {(H, W)}")
+    _image_sides(H, W)
     taps, r = _check_taps(taps)
-    if isinstance(want, str) or not all(isinstance(n, str) and n in TEXTURE_PLANES for n in want) or \
-            len(set(want)) != len(tuple(want)):
-        raise ValueError(f"want must name distinct planes among {TEXTURE_PLANES}, got {want!r}")
-    want = tuple(want)
+    ch, cw, want = _want_and_cells(want, TEXTURE_PLANES, cell_size)
     if floor is not None:
-        fl = _real(floor, "floor")
-        with np.errstate(over="ignore"):
-            fl = np.float32(fl)
-        if not (np.isfinite(fl) and fl > 0):
-            raise ValueError(f"floor must be finite and positive as float32, got {floor!r}")
-        floor = float(fl)
+        floor = _positive_f32(floor, "floor")
     elif "weight" in want or cell_size is not None:
         raise ValueError("the weight and the per-cell counts need a floor")
-    ch, cw = (None, None) if cell_size is None else _cell_size_hw(cell_size)
-    if not want and cell_size is None:
-        raise ValueError("no output was asked for")
     return H, W, dtype, taps, r, floor, ch, cw, want
 
 
@@ -304,50 +343,22 @@ def flow_affine_moments_params(flow, weight=None, cell_size=None, prior=None, cl
     cell grid.  prior: a finite 2 x 3 matrix in the centred frame, with clip > 0.  ValueError for anything the C entry would
     refuse."""
     H, W = _check_flow(flow)
-    ch, cw = (H, W) if cell_size is None else _cell_size_hw(cell_size)
-    kind = L.MA_SMOOTH_WEIGHT_NONE
-    if weight is not None:
-        wshape, wdtype = tuple(getattr(weight, "shape", ())), getattr(weight, "dtype", None)
-        if not isinstance(weight, (np.ndarray, DeviceArray)):
-            raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
-        cells = (-(-H // ch), -(-W // cw))
-        if wshape == (H, W) and wdtype == np.float32:
-            kind = L.MA_SMOOTH_WEIGHT_F32
-        elif wshape == (H, W) and wdtype == np.uint8:
-            kind = L.MA_SMOOTH_WEIGHT_U8
-        elif cell_size is not None and wshape == cells and wdtype == np.float32:
-            kind = L.MA_SMOOTH_WEIGHT_CELLS
-        elif cell_size is not None:
-            raise ValueError(f"a weight must be float32 or uint8 of shape {(H, W)}, or float32 of shape {cells} for cells "
-                             f"{(ch, cw)}, got {wdtype} {wshape}")
-        else:
-            raise ValueError(f"a per-pixel weight must be float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+    kind, ch, cw = _weight_kind(weight, H, W, cell_size, "grid")
     if prior is None:
         if clip is not None:
             raise ValueError("clip only has a meaning together with a prior")
         return H, W, kind, ch, cw, None, 0.0
-    try:
-        t = np.array(prior, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("prior must be a 2 x 3 matrix") from None
-    if t.shape != (2, 3) or not np.all(np.isfinite(t)):
-        raise ValueError("prior must be a finite 2 x 3 matrix")
+    pr = _matrix_2x3(prior, "prior")
     c = _real(clip, "clip")
     if not c > 0:
         raise ValueError(f"clip must be > 0, got {clip!r}")
-    return H, W, kind, ch, cw, np.ascontiguousarray(t).ravel(), c
+    return H, W, kind, ch, cw, pr, c
 
 
 def flow_affine_apply_params(flow, mat):
     """Checks of apply(flow, A) (include/microaligner_flowaffine.h) without touching a device: (H, W, A as 6 float64)."""
     H, W = _check_flow(flow)
-    try:
-        a = np.array(mat, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("the matrix must be 2 x 3") from None
-    if a.shape != (2, 3) or not np.all(np.isfinite(a)):
-        raise ValueError("the matrix must be a finite 2 x 3 matrix")
-    return H, W, np.ascontiguousarray(a).ravel()
+    return H, W, _matrix_2x3(mat, "the matrix")
 
 
 # ---- intensity-based affine alignment (include/microaligner_direct.h) ------------------------------------------------------
@@ -369,46 +380,21 @@ def direct_affine_moments_params(ref, mov, M, gain=1.0, bias=0.0, weight=None, c
     H, W = (int(v) for v in ref.shape)
     if tuple(mov.shape) != (H, W):
         raise ValueError(f"ref and mov must have one shape, got {tuple(ref.shape)} and {tuple(mov.shape)}")
-    if not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
-        raise ValueError(f"image sides must be in [1, 2^24], got {(H, W)}")
-    try:
-        m = np.array(M, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("M must be a 2 x 3 matrix") from None
-    if m.shape != (2, 3) or not np.all(np.isfinite(m)):
-        raise ValueError("M must be a finite 2 x 3 matrix")
+    _image_sides(H, W)
+    m = _matrix_2x3(M, "M")
     gain, bias = _real(gain, "gain"), _real(bias, "bias")
     if not (np.isfinite(gain) and np.isfinite(bias)):
         raise ValueError(f"gain and bias must be finite, got {gain!r}, {bias!r}")
-    kind = L.MA_SMOOTH_WEIGHT_NONE
-    if weight is not None:
-        wshape, wdtype = tuple(getattr(weight, "shape", ())), getattr(weight, "dtype", None)
-        if not isinstance(weight, (np.ndarray, DeviceArray)):
-            raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
-        if wshape == (H, W) and wdtype == np.float32:
-            kind = L.MA_SMOOTH_WEIGHT_F32
-        elif wshape == (H, W) and wdtype == np.uint8:
-            kind = L.MA_SMOOTH_WEIGHT_U8
-        else:
-            raise ValueError(f"the weight must be per pixel, float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+    kind = _weight_kind(weight, H, W)[0]
     c = 0.0
     if clip is not None:
         c = _real(clip, "clip")
         if not c > 0:
             raise ValueError(f"clip must be > 0, got {clip!r}")
-    return H, W, rdt, mdt, np.ascontiguousarray(m).ravel(), gain, bias, kind, c
+    return H, W, rdt, mdt, m, gain, bias, kind, c
 
 
 # ---- refining a flow against the images (include/microaligner_flowrefine.h) ------------------------------------------------
-def _positive_f32(v, name):
-    x = _real(v, name)
-    with np.errstate(over="ignore"):
-        x = np.float32(x)
-    if not (np.isfinite(x) and x > 0):
-        raise ValueError(f"{name} must be finite and positive as float32, got {v!r}")
-    return float(x)
-
-
 def flow_refine_step_params(ref, warped, flow, taps, floor, weight=None, max_step=1.0):
     """Checks and host-side arguments of one refinement step (include/microaligner_flowrefine.h) without touching a device:
     (H, W, ref dtype code, taps as C-contiguous float32, r, floor as float32, weight kind, max_step as float32).  ref: an
@@ -423,31 +409,12 @@ def flow_refine_step_params(ref, warped, flow, taps, floor, weight=None, max_ste
                          f"{tuple(getattr(warped, 'shape', ()))}")
     taps, r = _check_taps(taps)
     floor, max_step = _positive_f32(floor, "floor"), _positive_f32(max_step, "max_step")
-    kind = L.MA_SMOOTH_WEIGHT_NONE
-    if weight is not None:
-        wshape, wdtype = tuple(getattr(weight, "shape", ())), getattr(weight, "dtype", None)
-        if not isinstance(weight, (np.ndarray, DeviceArray)):
-            raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
-        if wshape == (H, W) and wdtype == np.float32:
-            kind = L.MA_SMOOTH_WEIGHT_F32
-        elif wshape == (H, W) and wdtype == np.uint8:
-            kind = L.MA_SMOOTH_WEIGHT_U8
-        else:
-            raise ValueError(f"the weight must be per pixel, float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
+    kind = _weight_kind(weight, H, W)[0]
     return H, W, rdt, taps, r, floor, kind, max_step
 
 
 # ---- local correlation maps of a registered pair (include/microaligner_localcorr.h) ----------------------------------------
 LOCALCORR_PLANES = ("score", "weight")
-
-
-def _finite_f32(v, name):
-    x = _real(v, name)
-    with np.errstate(over="ignore"):
-        x = np.float32(x)
-    if not np.isfinite(x):
-        raise ValueError(f"{name} must be finite as float32, got {v!r}")
-    return float(x)
 
 
 def local_correlation_params(ref, img, taps, floor, center=(0.0, 0.0), weight=None, lo=0.25, hi=0.75, min_support=0.0,
@@ -459,8 +426,7 @@ def local_correlation_params(ref, img, taps, floor, center=(0.0, 0.0), weight=No
     of "score" and "weight" to make.  ValueError for anything the C entry would refuse."""
     rdt = _check_image(ref, "ref")
     H, W = (int(v) for v in ref.shape)
-    if not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
-        raise ValueError(f"image sides must be in [1, 2^24], got {(H, W)}")
+    _image_sides(H, W)
     if not isinstance(img, (np.ndarray, DeviceArray)) or img.dtype != np.float32 or tuple(img.shape) != (H, W):
         raise ValueError(f"img must be float32 of shape {(H, W)}, got {getattr(img, 'dtype', None)} "
                          f"{tuple(getattr(img, 'shape', ()))}")
@@ -477,24 +443,8 @@ def local_correlation_params(ref, img, taps, floor, center=(0.0, 0.0), weight=No
     lo, hi = _finite_f32(lo, "lo"), _finite_f32(hi, "hi")
     if not -1.0 <= lo < hi <= 1.0:
         raise ValueError(f"lo and hi must satisfy -1 <= lo < hi <= 1 as float32, got {lo!r}, {hi!r}")
-    kind = L.MA_SMOOTH_WEIGHT_NONE
-    if weight is not None:
-        wshape, wdtype = tuple(getattr(weight, "shape", ())), getattr(weight, "dtype", None)
-        if not isinstance(weight, (np.ndarray, DeviceArray)):
-            raise ValueError(f"weight must be a numpy array or a DeviceArray, got {type(weight).__name__}")
-        if wshape == (H, W) and wdtype == np.float32:
-            kind = L.MA_SMOOTH_WEIGHT_F32
-        elif wshape == (H, W) and wdtype == np.uint8:
-            kind = L.MA_SMOOTH_WEIGHT_U8
-        else:
-            raise ValueError(f"the weight must be per pixel, float32 or uint8 of shape {(H, W)}, got {wdtype} {wshape}")
-    if isinstance(want, str) or not all(isinstance(n, str) and n in LOCALCORR_PLANES for n in want) or \
-            len(set(want)) != len(tuple(want)):
-        raise ValueError(f"want must name distinct planes among {LOCALCORR_PLANES}, got {want!r}")
-    want = tuple(want)
-    ch, cw = (None, None) if cell_size is None else _cell_size_hw(cell_size)
-    if not want and cell_size is None:
-        raise ValueError("no output was asked for")
+    kind = _weight_kind(weight, H, W)[0]
+    ch, cw, want = _want_and_cells(want, LOCALCORR_PLANES, cell_size)
     return H, W, rdt, taps, r, (ca, cb), floor, kind, ms, lo, hi, ch, cw, want
 
 
@@ -1551,6 +1501,21 @@ class Context:
         self._run(self.lib.ma_invert_flow, flow.ptr, H, W, max_iter, tol, out.ptr, residual.ptr, C.byref(count))
         return out, InvertInfo(int(count.value), residual)
 
+    def _flow_out(self, out, H, W):
+        """the `out` of a call that may write its flow in place: a new (H, W, 2) float32 array for None"""
+        if out is None:
+            return self.empty((H, W, 2), np.float32)
+        if not isinstance(out, DeviceArray) or out.dtype != np.float32 or out.shape != (H, W, 2):
+            raise ValueError(f"out must be a float32 DeviceArray of shape {(H, W, 2)}")
+        return out
+
+    def _class_counts(self, H, W, ch, cw, classes):
+        """the (gy, gx, classes) int64 array of per-cell counts and its pointer for the C entry; None twice without cells"""
+        if ch is None:
+            return None, None
+        counts = np.empty(self._cell_grid_shape(H, W, min(ch, H), min(cw, W)) + (classes,), np.int64)
+        return counts, counts.ctypes.data_as(C.POINTER(C.c_longlong))
+
     def smooth_flow(self, flow, taps, weight=None, cell_size=None, where="all", min_support=0.0, return_info=False, out=None):
         """The weighted smoothing of a flow with the symmetric kernel taps t[0 .. r] (include/microaligner_flowsmooth.h): a
         row pass and a column pass over w*u, w*v, w, the divide, and for where="blend" the feathering back into the
@@ -1558,10 +1523,7 @@ class Context:
         float32 map), a new device array out; `out` may name the array to write instead, `flow` itself included.  With
         return_info a SmoothInfo(unsupported) beside it, at the cost of a synchronisation."""
         H, W, taps, r, kind, ch, cw, mode, ms = smooth_flow_params(flow, taps, weight, cell_size, where, min_support)
-        if out is None:
-            out = self.empty((H, W, 2), np.float32)
-        elif not isinstance(out, DeviceArray) or out.dtype != np.float32 or out.shape != (H, W, 2):
-            raise ValueError(f"out must be a float32 DeviceArray of shape {(H, W, 2)}")
+        out = self._flow_out(out, H, W)
         count = C.c_longlong(0)
         self._run(self.lib.ma_smooth_flow, flow.ptr, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r,
                   None if weight is None else weight.ptr, kind, ch, cw, mode, ms, out.ptr,
@@ -1621,13 +1583,9 @@ class Context:
         H, W, dtype, taps, r, floor, ch, cw, want = texture_maps_params(img, taps, floor, cell_size, want)
         out = {n: self.empty((H, W), np.float32) for n in want}
         ptr = {n: (out[n].ptr if n in out else None) for n in TEXTURE_PLANES}
-        counts = None
-        if ch is not None:
-            gy, gx = self._cell_grid_shape(H, W, min(ch, H), min(cw, W))
-            counts = np.empty((gy, gx, L.MA_TEXTURE_CLASSES), np.int64)
+        counts, counts_ptr = self._class_counts(H, W, ch, cw, L.MA_TEXTURE_CLASSES)
         self._run(self.lib.ma_texture_maps, img.ptr, dtype, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r,
-                  0.0 if floor is None else floor, ptr["lam_min"], ptr["lam_max"], ptr["weight"], ch or 0, cw or 0,
-                  None if counts is None else counts.ctypes.data_as(C.POINTER(C.c_longlong)))
+                  0.0 if floor is None else floor, ptr["lam_min"], ptr["lam_max"], ptr["weight"], ch or 0, cw or 0, counts_ptr)
         if counts is not None:
             out["counts"] = counts
         return out
@@ -1645,13 +1603,10 @@ class Context:
             ref, img, taps, floor, center, weight, lo, hi, min_support, cell_size, want)
         out = {n: self.empty((H, W), np.float32) for n in want}
         ptr = {n: (out[n].ptr if n in out else None) for n in LOCALCORR_PLANES}
-        counts = None
-        if ch is not None:
-            gy, gx = self._cell_grid_shape(H, W, min(ch, H), min(cw, W))
-            counts = np.empty((gy, gx, L.MA_LOCALCORR_CLASSES), np.int64)
+        counts, counts_ptr = self._class_counts(H, W, ch, cw, L.MA_LOCALCORR_CLASSES)
         self._run(self.lib.ma_local_correlation, ref.ptr, rdt, img.ptr, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r,
                   ca, cb, floor, None if weight is None else weight.ptr, kind, ms, lo, hi, ptr["score"], ptr["weight"],
-                  ch or 0, cw or 0, None if counts is None else counts.ctypes.data_as(C.POINTER(C.c_longlong)))
+                  ch or 0, cw or 0, counts_ptr)
         if counts is not None:
             out["counts"] = counts
         return out
@@ -1665,10 +1620,7 @@ class Context:
         write instead, `flow` itself included.  With return_info a RefineStepInfo(step_max, clamped, invalid) beside it, at
         the cost of a synchronisation."""
         H, W, rdt, taps, r, floor, kind, max_step = flow_refine_step_params(ref, warped, flow, taps, floor, weight, max_step)
-        if out is None:
-            out = self.empty((H, W, 2), np.float32)
-        elif not isinstance(out, DeviceArray) or out.dtype != np.float32 or out.shape != (H, W, 2):
-            raise ValueError(f"out must be a float32 DeviceArray of shape {(H, W, 2)}")
+        out = self._flow_out(out, H, W)
         stats = (C.c_longlong * L.MA_REFINE_STATS)()
         self._run(self.lib.ma_flow_refine_step, ref.ptr, rdt, warped.ptr, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r,
                   floor, None if weight is None else weight.ptr, kind, max_step, flow.ptr, out.ptr,
@@ -1699,10 +1651,7 @@ class Context:
         relative to it (join).  A device array in, a new device array out; `out` may name the array to write instead,
         `flow` itself included."""
         H, W, a = flow_affine_apply_params(flow, mat)
-        if out is None:
-            out = self.empty((H, W, 2), np.float32)
-        elif not isinstance(out, DeviceArray) or out.dtype != np.float32 or out.shape != (H, W, 2):
-            raise ValueError(f"out must be a float32 DeviceArray of shape {(H, W, 2)}")
+        out = self._flow_out(out, H, W)
         self._run(self.lib.ma_flow_affine_apply, flow.ptr, H, W, a.ctypes.data_as(C.POINTER(C.c_double)), out.ptr)
         return out
 

@@ -252,6 +252,6 @@ def test_the_source_is_built_and_off_the_measured_path():
     assert build.source_hash() == "7f5e1df0cf7595ec"
     assert "local_correlation.hip" in build.SOURCES and "microaligner_localcorr.h" not in " ".join(build.HEADERS)
     assert [os.path.basename(h) for h in build.SOURCE_HEADERS["local_correlation.hip"]] == \
-        ["microaligner_localcorr.h", "microaligner_flowsmooth.h", "cell_grid.h", "window_fir.h"]
+        ["microaligner_localcorr.h", "microaligner_flowsmooth.h", "cell_grid.h", "window_fir.h", "weight_map.h"]
     users = open(os.path.join(build.CSRC, "window_fir.h")).read().split("#pragma once")[0]
     assert "local_correlation.hip" in users

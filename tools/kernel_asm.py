@@ -2,7 +2,10 @@
 
     python tools/kernel_asm.py dump DIR [TREE]     device assembly of every source of build.SOURCES into DIR; TREE: a checkout
                                                    of another commit (default: this tree), compiled with its own build.FLAGS
-    python tools/kernel_asm.py compare OLD NEW     per kernel: instruction stream and .amdhsa_* descriptor, OLD against NEW
+    python tools/kernel_asm.py compare OLD NEW [A=B ...]
+                                                   per kernel: instruction stream and .amdhsa_* descriptor, OLD against NEW;
+                                                   A=B: a type that a kernel takes by value and that was renamed (its
+                                                   name is part of the mangled name): A becomes B in OLD's text first
 
 `compare` splits each file at the kernels' function labels, so that a kernel may move within its file, masks what only
 numbers the functions of a file (.LBB<n>_, BB<n>_ in the loop comments and their padding, .Lfunc_end<n>) and the per-compilation __hip_cuid_<hex> symbol, and exits non-zero if a kernel of OLD is missing
@@ -33,9 +36,11 @@ def dump(out, tree=ROOT):
                 sys.exit(r.stderr)
 
 
-def kernels(path):
+def kernels(path, renamed=()):
     """{mangled name: masked text from the kernel's .type line to its .Lfunc_end}, and the masked whole file"""
     text = open(path).read()
+    for a, b in renamed:
+        text = text.replace(a, b)
     for pat, to in MASK:
         text = pat.sub(to, text)
     names = re.findall(r"^\s*\.amdhsa_kernel (\S+)$", text, re.M)
@@ -46,14 +51,14 @@ def kernels(path):
     return out, text
 
 
-def compare(old, new):
+def compare(old, new, renamed=()):
     bad = 0
     for f in sorted(os.listdir(old)):
         if not os.path.exists(os.path.join(new, f)):
             print(f"{f}: missing in {new}")
             bad += 1
             continue
-        (ko, to), (kn, tn) = kernels(os.path.join(old, f)), kernels(os.path.join(new, f))
+        (ko, to), (kn, tn) = kernels(os.path.join(old, f), renamed), kernels(os.path.join(new, f))
         diff = [n for n in ko if ko[n] != kn.get(n)]
         whole = "whole file identical" if to == tn else "file differs outside the kernels or in their order"
         if not ko and to != tn:
@@ -70,7 +75,7 @@ def compare(old, new):
 if __name__ == "__main__":
     if len(sys.argv) in (3, 4) and sys.argv[1] == "dump":
         dump(*sys.argv[2:])
-    elif len(sys.argv) == 4 and sys.argv[1] == "compare":
-        sys.exit(1 if compare(sys.argv[2], sys.argv[3]) else 0)
+    elif len(sys.argv) >= 4 and sys.argv[1] == "compare" and all(a.count("=") == 1 for a in sys.argv[4:]):
+        sys.exit(1 if compare(sys.argv[2], sys.argv[3], [a.split("=") for a in sys.argv[4:]]) else 0)
     else:
         sys.exit(__doc__)
