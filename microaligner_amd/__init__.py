@@ -12,7 +12,7 @@ from .optflow_reg import OptFlowRegistrator, TileFlowCalc, Warper, farneback, co
     invert_flow, transform_points, FlowGrid, FlowGridError, compress_flow, flow_grid_error, smooth_flow, fold_mask, \
     repair_flow, fit_flow_affine, split_flow, join_flow, local_affine, FlowAffineInfo, FlowAffineMaps, \
     refine_flow, FlowRefineInfo, LandmarkFit, fit_landmarks, landmark_flow, landmark_points, median_flow, outlier_mask, \
-    MedianInfo
+    MedianInfo, fill_flow, FillInfo
 from .shared_modules.registration_qc import FlowQC, RegistrationQC, assess_registration, flow_qc
 from .shared_modules.residual_shift import ResidualShift, ShiftMaps, residual_shift
 from .shared_modules.texture import TextureMaps, texture_maps
@@ -27,5 +27,5 @@ __all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc",
            "FlowAffineMaps", "texture_maps", "TextureMaps", "align_affine", "DirectAffineInfo", "refine_flow", "FlowRefineInfo",
            "LandmarkFit", "fit_landmarks", "landmark_flow", "landmark_points", "align_translation", "TranslationInfo",
            "normalize_percentile", "NormalizeInfo", "local_correlation", "CorrelationMaps", "median_flow", "outlier_mask",
-           "MedianInfo"]
+           "MedianInfo", "fill_flow", "FillInfo"]
 __version__ = "0.1.0"

@@ -285,6 +285,12 @@ FLOWMEDIAN_SIGNATURES = {
     "ma_median_flow": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_flowfill.h (push-pull fill of a flow); the weight
+# kinds are those of microaligner_flowsmooth.h
+FLOWFILL_SIGNATURES = {
+    "ma_fill_flow": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, C.POINTER(C.c_longlong)]),
+}
+
 _lib = None
 
 
@@ -304,7 +310,8 @@ def load():
             list(FLOWAFFINE_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + \
             list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()) + \
             list(LANDMARK_SIGNATURES.items()) + list(TRANSLATION_SIGNATURES.items()) + \
-            list(QUANTILE_SIGNATURES.items()) + list(LOCALCORR_SIGNATURES.items()) + list(FLOWMEDIAN_SIGNATURES.items()):
+            list(QUANTILE_SIGNATURES.items()) + list(LOCALCORR_SIGNATURES.items()) + list(FLOWMEDIAN_SIGNATURES.items()) + \
+            list(FLOWFILL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
            "flow_compose.hip", "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip", "texture.hip", "direct_affine.hip", "flow_refine.hip",
-           "landmarks.hip", "translation.hip", "quantile.hip", "local_correlation.hip", "flow_median.hip"]
+           "landmarks.hip", "translation.hip", "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip"]
 HEADERS = [os.path.join(CSRC, "ma_internal.h"), os.path.join(CSRC, "remap_common.h"), os.path.join(CSRC, "nmi_score.h"),
            os.path.join(HERE, "..", "include", "microaligner_hip.h")]
 # headers of single sources that are off the measured path (not in HEADERS, so not in source_hash())
@@ -26,7 +26,7 @@ _FLOW_GRID = [os.path.join(HERE, "..", "include", "microaligner_flowgrid.h"), os
 _FLOW_JACOBIAN = os.path.join(CSRC, "flow_jacobian.h")   # det J, stated once for the quality maps and the fold mask
 # the separable FIR tile of the smoothing, the texture maps, the refinement and the local correlation maps
 _WINDOW_FIR = os.path.join(CSRC, "window_fir.h")
-# the weight argument of the six calls that take one: its readers on the device, its check and dispatch at the C entry
+# the weight argument of the seven calls that take one: its readers on the device, its check and dispatch at the C entry
 _WEIGHT_MAP = os.path.join(CSRC, "weight_map.h")
 SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_qc.h"), _CELL_GRID, _FLOW_JACOBIAN],
                   "remap_interp.hip": _INTERP_HEADERS,
@@ -51,7 +51,9 @@ SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_q
                                             os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID,
                                             _WINDOW_FIR, _WEIGHT_MAP],
                   "flow_median.hip": [os.path.join(HERE, "..", "include", "microaligner_flowmedian.h"),
-                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP]}
+                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP],
+                  "flow_fill.hip": [os.path.join(HERE, "..", "include", "microaligner_flowfill.h"),
+                                    os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP]}
 # the grid-flow headers are also read by the two sources whose kernels take their flow from a grid: further dependencies of
 # those sources, beside the headers of their own above
 GRID_FLOW_USERS = {"warp_compose.hip": _FLOW_GRID, "flow_invert.hip": _FLOW_GRID}
@@ -115,15 +117,16 @@ def source_hash():
     #     image_quantiles() / normalize_percentile() / a `percentiles` argument reach;
     #   - the local correlation maps (windowed ZNCC of a registered pair), which only local_correlation() reaches;
     #   - the median filter of a flow and its outlier mask, which only median_flow() / outlier_mask() reach;
+    #   - the push-pull fill of a flow (a weighted pyramid pulled to 1 x 1 and pushed back), which only fill_flow() reaches;
     #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps, flow_jacobian.h, det J of
     #     the quality maps and the fold mask, window_fir.h, the separable FIR tile of the flow smoothing, the texture
-    #     maps, the flow refinement and the local correlation maps, and weight_map.h, the weight argument of the six
+    #     maps, the flow refinement and the local correlation maps, and weight_map.h, the weight argument of the seven
     #     calls above that take one (SOURCE_HEADERS).
     off_path = {"probe.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "affine.hip", "qc.hip",
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
                 "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip",
                 "texture.hip", "direct_affine.hip", "flow_refine.hip", "landmarks.hip", "translation.hip",
-                "quantile.hip", "local_correlation.hip", "flow_median.hip"}
+                "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip"}
     for path in [os.path.join(CSRC, s) for s in SOURCES if s not in off_path] + HEADERS:
         h.update(open(path, "rb").read())
     h.update(" ".join(_flags()).encode())

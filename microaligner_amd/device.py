@@ -214,7 +214,7 @@ def _weight_kind(weight, H, W, cell_size=None, cells=None):
     map as far as `cells` says the call takes one:
       None    never (direct_affine_moments, flow_refine_step, local_correlation); cell_size is not theirs to pass;
       "map"   with cell_size a (gy, gx) float32 map on that cell grid and nothing else; cell_size has no meaning without
-              one (smooth_flow, median_flow);
+              one (smooth_flow, median_flow, fill_flow);
       "grid"  cell_size is the grid of the call whatever the weight, None standing for one cell, and the weight is per
               pixel or a float32 map of the grid's shape (flow_affine_moments).
     cell_h, cell_w: the cells, (H, W) for the one cell of "grid", else (1, 1)."""
@@ -307,6 +307,18 @@ def median_flow_params(flow, radius=2, weight=None, cell_size=None, where="all",
         raise ValueError(f"generic must be a bool, got {generic!r}")
     kind, ch, cw = _weight_kind(weight, H, W, cell_size, "map")
     return H, W, int(radius), kind, ch, cw, MEDIAN_MODES[where], float(th), L.MA_MEDIAN_GENERIC if generic else 0
+
+
+# ---- push-pull fill of a flow (include/microaligner_flowfill.h) ------------------------------------------------------------
+def fill_flow_params(flow, weight=None, cell_size=None):
+    """Checks and host-side arguments of the push-pull fill (include/microaligner_flowfill.h) without touching a device:
+    (H, W, weight kind, cell_h, cell_w, levels).  weight: what it is for smooth_flow.  levels: the number of pyramid levels
+    above the flow.  ValueError for anything the C entry would refuse."""
+    H, W = _check_flow(flow)
+    if -(-H // 8) * -(-W // 128) > 0x7fffffff:
+        raise ValueError(f"flow too large: more than 2^31 - 1 tiles of 8 x 128 pixels in {(H, W)}")
+    kind, ch, cw = _weight_kind(weight, H, W, cell_size, "map")
+    return H, W, kind, ch, cw, (max(H, W) - 1).bit_length()
 
 
 # ---- texture support maps of an image (include/microaligner_texture.h) ----------------------------------------------------
@@ -537,6 +549,12 @@ class MedianInfo(collections.namedtuple("MedianInfo", "outliers dropped unsuppor
     """median_flow(..., return_info=True): participating pixels farther than thresh from the median of their window,
     pixels that do not participate (weight or value), and those of them whose window holds no participating pixel at all
     (their median is NaN)."""
+
+
+class FillInfo(collections.namedtuple("FillInfo", "dropped blended unsupported levels")):
+    """fill_flow(..., return_info=True): pixels that were filled (weight NaN, negative or 0, or a flow that is not finite),
+    pixels blended with the fill (a weight in (0, 1)), output pixels with a non-finite component (all of them where every
+    pixel was dropped), and the number of pyramid levels above the flow."""
 
 
 class RepairInfo(collections.namedtuple("RepairInfo", "rounds converged")):
@@ -1573,6 +1591,21 @@ class Context:
         if return_info:
             res.append(MedianInfo(*(int(v) for v in counts)))
         return res[0] if len(res) == 1 else tuple(res)
+
+    def fill_flow(self, flow, weight=None, cell_size=None, return_info=False, out=None):
+        """The push-pull fill of a flow (include/microaligner_flowfill.h): a weighted pyramid pulled to 1 x 1 and pushed
+        back, pixels of weight >= 1 coming back bit for bit.  Device arrays in (weight: None, an (H, W) float32 or uint8
+        array, or with cell_size a (gy, gx) float32 map), a new device array out; `out` may name the array to write instead,
+        `flow` itself included, never the weight.  With return_info a FillInfo(dropped, blended, unsupported, levels)
+        beside it, at the cost of a synchronisation."""
+        H, W, kind, ch, cw, levels = fill_flow_params(flow, weight, cell_size)
+        if out is not None and out is weight:
+            raise ValueError("out must not be the weight")
+        out = self._flow_out(out, H, W)
+        counts = (C.c_longlong * 3)()
+        self._run(self.lib.ma_fill_flow, flow.ptr, H, W, None if weight is None else weight.ptr, kind, ch, cw, out.ptr,
+                  counts if return_info else None)
+        return (out, FillInfo(*(int(v) for v in counts), levels)) if return_info else out
 
     def texture_maps(self, img, taps, floor=None, cell_size=None, want=("lam_min", "lam_max")):
         """The texture support maps of an (H, W) uint8, uint16 or float32 device image with the symmetric kernel taps
