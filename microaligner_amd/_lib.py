@@ -291,6 +291,11 @@ FLOWFILL_SIGNATURES = {
     "ma_fill_flow": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_debug.h (test hook: fill idle scratch memory)
+DEBUG_SIGNATURES = {
+    "ma_debug_fill_idle": (_i, [_vp, _i, C.POINTER(C.c_ulonglong)]),
+}
+
 _lib = None
 
 
@@ -311,7 +316,7 @@ def load():
             list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()) + \
             list(LANDMARK_SIGNATURES.items()) + list(TRANSLATION_SIGNATURES.items()) + \
             list(QUANTILE_SIGNATURES.items()) + list(LOCALCORR_SIGNATURES.items()) + list(FLOWMEDIAN_SIGNATURES.items()) + \
-            list(FLOWFILL_SIGNATURES.items()):
+            list(FLOWFILL_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
            "flow_compose.hip", "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip", "texture.hip", "direct_affine.hip", "flow_refine.hip",
-           "landmarks.hip", "translation.hip", "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip"]
+           "landmarks.hip", "translation.hip", "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip", "debug_fill.hip"]
 HEADERS = [os.path.join(CSRC, "ma_internal.h"), os.path.join(CSRC, "remap_common.h"), os.path.join(CSRC, "nmi_score.h"),
            os.path.join(HERE, "..", "include", "microaligner_hip.h")]
 # headers of single sources that are off the measured path (not in HEADERS, so not in source_hash())
@@ -53,7 +53,8 @@ SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_q
                   "flow_median.hip": [os.path.join(HERE, "..", "include", "microaligner_flowmedian.h"),
                                       os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP],
                   "flow_fill.hip": [os.path.join(HERE, "..", "include", "microaligner_flowfill.h"),
-                                    os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP]}
+                                    os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP],
+                  "debug_fill.hip": [os.path.join(HERE, "..", "include", "microaligner_debug.h")]}
 # the grid-flow headers are also read by the two sources whose kernels take their flow from a grid: further dependencies of
 # those sources, beside the headers of their own above
 GRID_FLOW_USERS = {"warp_compose.hip": _FLOW_GRID, "flow_invert.hip": _FLOW_GRID}
@@ -118,6 +119,7 @@ def source_hash():
     #   - the local correlation maps (windowed ZNCC of a registered pair), which only local_correlation() reaches;
     #   - the median filter of a flow and its outlier mask, which only median_flow() / outlier_mask() reach;
     #   - the push-pull fill of a flow (a weighted pyramid pulled to 1 x 1 and pushed back), which only fill_flow() reaches;
+    #   - the test hook that fills a context's idle scratch memory, which only tests call and which launches no kernel;
     #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps, flow_jacobian.h, det J of
     #     the quality maps and the fold mask, window_fir.h, the separable FIR tile of the flow smoothing, the texture
     #     maps, the flow refinement and the local correlation maps, and weight_map.h, the weight argument of the seven
@@ -126,7 +128,7 @@ def source_hash():
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
                 "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip",
                 "texture.hip", "direct_affine.hip", "flow_refine.hip", "landmarks.hip", "translation.hip",
-                "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip"}
+                "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip", "debug_fill.hip"}
     for path in [os.path.join(CSRC, s) for s in SOURCES if s not in off_path] + HEADERS:
         h.update(open(path, "rb").read())
     h.update(" ".join(_flags()).encode())

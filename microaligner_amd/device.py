@@ -1103,6 +1103,16 @@ class Context:
     def sync(self):
         L.check(self.lib.ma_sync(self.handle))
 
+    def debug_fill_idle(self, byte):
+        """Test hook (include/microaligner_debug.h): wait for every stream of this context and of its companion, then set
+        every byte of their idle scratch memory -- workspace, free buffers of the C-side cache, the small device buffer and
+        the page-locked result buffer -- to `byte` (0 .. 255).  Returns the bytes filled of each of the four kinds."""
+        if isinstance(byte, bool) or not isinstance(byte, (int, np.integer)) or not 0 <= int(byte) <= 255:
+            raise ValueError(f"byte must be an integer in 0..255, got {byte!r}")
+        filled = (C.c_ulonglong * 4)()
+        L.check(self.lib.ma_debug_fill_idle(self.handle, int(byte), filled))
+        return tuple(int(v) for v in filled)
+
     # -- options / transfer engines ------------------------------------------------------------
     def set_option(self, option, value):
         L.check(self.lib.ma_ctx_set_option(self.handle, int(option), int(value)))
