@@ -26,6 +26,9 @@
 #define MICROALIGNER_COMPOSE_H
 
 #include "microaligner_hip.h"
+/* Device pointers follow the alignment rule of microaligner_hip.h ("Device pointers"): an array is aligned to its element,
+ * a flow, a map or the nodes of a grid flow to 8 bytes, float64 points to 16 bytes, unless an entry below names a stricter
+ * figure for one argument; below the rule an entry returns MA_EINVAL before it launches anything. */
 
 #ifdef __cplusplus
 extern "C" {

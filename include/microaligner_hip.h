@@ -23,6 +23,18 @@
  *    the host synchronise that stream, the others do not (call ma_sync).
  *  - One ma_ctx per device per process; a ctx is not thread-safe.
  *  - dtype: MA_U8 / MA_U16 / MA_F32.
+ *  - Device pointers (the alignment rule of this header and of every extension header).  A device pointer is
+ *    aligned to its element: 1, 2, 4 or 8 bytes.  An array of pairs -- a flow, a map, the nodes of a grid flow,
+ *    points -- is aligned to the pair: 8 bytes for pairs of float32, 16 bytes for pairs of float64.  The only
+ *    stricter requirements are those the comment of an entry names for one argument: `cw` of ma_landmark_flow
+ *    and ma_landmark_points at 32 bytes, `dst` of ma_pyr_up_flow at 16 bytes, and `flow_out` of
+ *    ma_optflow_register, which ends in that call, at 16 bytes.  Within the rule every result is the same as at
+ *    an address aligned to 64 KiB: an entry may load 16 bytes at a time where the address allows and element by
+ *    element where not, and both give the same bits (the float64 sums of ma_flow_affine_moments, whose order of
+ *    summation follows the load width, are the same to within their stated bound).  Below the rule an entry
+ *    returns MA_EINVAL, with the argument's name in ma_last_error(), before it launches or enqueues anything:
+ *    every array of pairs and every argument named above is checked (a pointer that is not even aligned to its
+ *    own element is a value no allocator or array arithmetic produces, and is not looked for).
  */
 #ifndef MICROALIGNER_HIP_H
 #define MICROALIGNER_HIP_H
@@ -231,7 +243,8 @@ int ma_farneback_debug(ma_ctx* ctx, const void* prev, const void* next, int dtyp
  * reference's class (optflow_registrator.py:54-59) plus the two rounding-model flag sets of this library.
  *
  * ref, mov: (H, W) device images of `dtype`; flow_out: (H, W, 2) float32 device buffer owned by the caller, with
- * mov(p) ~ ref(p + flow(p)).  reports (may be NULL): one record per pyramid level, smallest level first -- what the
+ * mov(p) ~ ref(p + flow(p)).  flow_out must be 16-byte aligned: it is the dst of the ma_pyr_up_flow that ends the call.
+ * reports (may be NULL): one record per pyramid level, smallest level first -- what the
  * reference prints (factor, MI scores, accept / reject); *n_reports receives the number of levels.  The call
  * synchronises the ctx stream once per level (the gate decision needs the NMI scores on the host); on return the
  * flow is enqueued, not necessarily complete (ma_sync).  MA_EINVAL when the pyramid would be empty: where the
@@ -317,7 +330,9 @@ int ma_merge_flows_tiled_cells(ma_ctx* ctx, const float* flow1, const float* flo
 int ma_pyr_down(ma_ctx* ctx, const void* src, int dtype, int h, int w, void* dst);
 /* cv2.pyrUp(flow * scale, dstsize=(dw, dh)) on a 2-channel float32 flow
  * (optflow_registrator.py:140,150,164,169,212,214); the numpy pre-multiply
- * (2, 4 or 1) is fused.  Requires |dw-2w| == dw%2 and |dh-2h| == dh%2. */
+ * (2, 4 or 1) is fused.  Requires |dw-2w| == dw%2 and |dh-2h| == dh%2.
+ * dst must be 16-byte aligned (it is written two pixels at a time); src is aligned
+ * to the pair, 8 bytes, as every flow ("Device pointers" above).  MA_EINVAL otherwise. */
 int ma_pyr_up_flow(ma_ctx* ctx, const float* src, int h, int w, float scale, float* dst, int dh, int dw);
 
 /* ---- DOG -------------------------------------------------------------------

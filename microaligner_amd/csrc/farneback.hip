@@ -1226,6 +1226,7 @@ int farneback_impl(ma_ctx* ctx, const void* prev, const void* next, int dtype, i
                    float* R0_out, float* R1_out, float* M0_out)
 {
     MA_REQUIRE(ctx && prev && next && flow_out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow_out, 8, "flow_out");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
     MA_REQUIRE(H > 0 && W > 0, "image must be non-empty");
     MA_REQUIRE(tile >= 0 && overlap >= 0, "tile/overlap must be >= 0");
@@ -1406,6 +1407,7 @@ int farneback_levels_impl(ma_ctx* ctx, const void* prev, const void* next, int d
         return farneback_impl(ctx, prev, next, dtype, H, W, 0, 0, winsize, iterations, poly_n, poly_sigma, flags, flow_out,
                               nullptr, nullptr, nullptr);
     MA_REQUIRE(ctx && prev && next && flow_out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow_out, 8, "flow_out");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
     MA_REQUIRE(H > 0 && W > 0, "image must be non-empty");
     MA_REQUIRE(winsize >= 1, "winsize must be >= 1");

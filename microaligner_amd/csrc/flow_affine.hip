@@ -193,7 +193,7 @@ extern "C" int ma_flow_affine_moments(ma_ctx* ctx, const float* flow, int H, int
     MA_REQUIRE(ctx && flow && sums_host && counts_host, "NULL argument");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FA_SIDE_MAX && W <= FA_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_TRY(ma_weight_check(weight, weight_kind, true, {}, cell_h, cell_w));   // writes host arrays only
-    MA_REQUIRE(((size_t)flow & 7) == 0, "flow must be 8-byte aligned");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
     FaPrior pr{};
     if (prior) {
         for (int k = 0; k < 6; k++) {
@@ -238,6 +238,8 @@ extern "C" int ma_flow_affine_moments(ma_ctx* ctx, const float* flow, int H, int
 extern "C" int ma_flow_affine_apply(ma_ctx* ctx, const float* flow, int H, int W, const double* a, float* out)
 {
     MA_REQUIRE(ctx && flow && a && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FA_SIDE_MAX && W <= FA_SIDE_MAX, "flow sides must be in [1, 2^24]");
     FaMat m;
     for (int k = 0; k < 6; k++) {

@@ -55,6 +55,9 @@ __global__ __launch_bounds__(256) void compose_flows_kernel(const float2* __rest
 extern "C" int ma_compose_flows(ma_ctx* ctx, const float* first, const float* second, int H, int W, float* out)
 {
     MA_REQUIRE(ctx && first && second && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(first, 8, "first");
+    MA_REQUIRE_ALIGNED(second, 8, "second");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FC_SIDE_MAX && W <= FC_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_REQUIRE(out != first, "out must not be first (it may be second)");
     MA_HIP(hipSetDevice(ctx->device));

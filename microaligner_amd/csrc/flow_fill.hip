@@ -218,6 +218,8 @@ extern "C" int ma_fill_flow(ma_ctx* ctx, const float* flow, int H, int W, const 
                             int cell_w, float* out, long long* counts_host)
 {
     MA_REQUIRE(ctx && flow && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FF_SIDE_MAX && W <= FF_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_TRY(ma_weight_check(weight, weight_kind, true, {out}, cell_h, cell_w));
     // level l has hs[l] x ws[l] entries; level l >= 1 starts at entry at[l] of the stored levels

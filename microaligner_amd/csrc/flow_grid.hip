@@ -118,6 +118,8 @@ extern "C" {
 int ma_flow_grid_sample(ma_ctx* ctx, const float* flow, int H, int W, int s, float* nodes)
 {
     MA_REQUIRE(ctx && flow && nodes, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
+    MA_REQUIRE_ALIGNED(nodes, 8, "nodes");
     MA_TRY(check_grid(H, W, s));
     const FgGrid g = fg_grid(nullptr, H, W, s);
     MA_HIP(hipSetDevice(ctx->device));
@@ -130,6 +132,8 @@ int ma_flow_grid_sample(ma_ctx* ctx, const float* flow, int H, int W, int s, flo
 int ma_flow_grid_expand(ma_ctx* ctx, const float* nodes, int H, int W, int s, float* out)
 {
     MA_REQUIRE(ctx && nodes && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(nodes, 8, "nodes");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     MA_TRY(check_grid(H, W, s));
     const FgGrid g = fg_grid(nodes, H, W, s);
     const int nty = (H + FG_TH - 1) / FG_TH;
@@ -145,6 +149,8 @@ int ma_flow_grid_error(ma_ctx* ctx, const float* flow, const float* nodes, int H
                        float tol, float* max_err, long long* above, long long* invalid)
 {
     MA_REQUIRE(ctx && flow && nodes && max_err && above && invalid, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
+    MA_REQUIRE_ALIGNED(nodes, 8, "nodes");
     MA_TRY(check_grid(H, W, s));
     MA_REQUIRE(tol == tol, "tol must not be NaN");
     MaCellGrid cg;

@@ -195,6 +195,8 @@ extern "C" int ma_invert_flow(ma_ctx* ctx, const float* flow, int H, int W, int 
                               float* residual, long long* not_converged_host)
 {
     MA_REQUIRE(ctx && flow && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FI_SIDE_MAX && W <= FI_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_REQUIRE(max_iter >= 1, "max_iter must be at least 1");
     MA_REQUIRE(std::isfinite(tol) && tol >= 0.f, "tol must be finite and not negative");
@@ -226,6 +228,8 @@ static int transform_points(ma_ctx* ctx, const double* pts, int n, const S& samp
                             double* out, unsigned char* converged, unsigned char* inside)
 {
     MA_REQUIRE(ctx && pts && out && converged && inside, "NULL argument");
+    MA_REQUIRE_ALIGNED(pts, 16, "pts");
+    MA_REQUIRE_ALIGNED(out, 16, "out");
     MA_REQUIRE(n >= 0, "the number of points must not be negative");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FI_SIDE_MAX && W <= FI_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_REQUIRE(direction == MA_POINTS_TO_MOVING || direction == MA_POINTS_TO_REFERENCE, "unknown direction");
@@ -251,6 +255,7 @@ extern "C" int ma_transform_points(ma_ctx* ctx, const double* pts, int n, const 
                                    double* out, unsigned char* converged, unsigned char* inside)
 {
     MA_REQUIRE(flow, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
     return transform_points(ctx, pts, n, DenseSampler64{(const float2*)flow, H, W}, H, W, m6, t6, pad_left, pad_top, direction,
                             max_iter, tol, out, converged, inside);
 }
@@ -261,6 +266,7 @@ extern "C" int ma_transform_points_grid(ma_ctx* ctx, const double* pts, int n, c
                                         unsigned char* inside)
 {
     MA_REQUIRE(nodes, "NULL argument");
+    MA_REQUIRE_ALIGNED(nodes, 8, "nodes");
     MA_REQUIRE(s >= 1, "the stride must be at least 1");
     MA_REQUIRE(H >= 1 && W >= 1, "flow sides must be in [1, 2^24]");
     return transform_points(ctx, pts, n, FgSampler64{fg_grid(nodes, H, W, s)}, H, W, m6, t6, pad_left, pad_top, direction,

@@ -258,6 +258,8 @@ extern "C" int ma_median_flow(ma_ctx* ctx, const float* flow, int H, int W, int 
                               long long* counts_host)
 {
     MA_REQUIRE(ctx && flow && (out || keep), "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     MA_REQUIRE(out != flow, "out and flow must be distinct arrays: a median reads its neighbours");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= MF_SIDE_MAX && W <= MF_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_REQUIRE(r >= 1 && r <= MA_MEDIAN_MAX_RADIUS, "r must be in [1, 7]");

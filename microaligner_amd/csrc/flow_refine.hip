@@ -155,6 +155,8 @@ extern "C" int ma_flow_refine_step(ma_ctx* ctx, const void* ref, int dtype, cons
                                    float max_step, const float* flow, float* out, long long* stats_host)
 {
     MA_REQUIRE(ctx && ref && warped && taps_host && flow && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FR_SIDE_MAX && W <= FR_SIDE_MAX, "image sides must be in [1, 2^24]");
     MA_REQUIRE(r >= 1 && r <= MA_REFINE_MAX_RADIUS, "r must be in [1, 128]");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "unknown dtype");

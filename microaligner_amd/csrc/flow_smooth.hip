@@ -245,6 +245,8 @@ extern "C" int ma_smooth_flow(ma_ctx* ctx, const float* flow, int H, int W, cons
                               long long* unsupported_host)
 {
     MA_REQUIRE(ctx && flow && taps_host && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FS_SIDE_MAX && W <= FS_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_REQUIRE(r >= 1 && r <= MA_SMOOTH_MAX_RADIUS, "r must be in [1, 128]");
     MA_TRY(ma_weight_check(weight, weight_kind, true, {out}, cell_h, cell_w));
@@ -274,6 +276,7 @@ extern "C" int ma_flow_fold_mask(ma_ctx* ctx, const float* flow, int H, int W, i
                                  long long* counts_host)
 {
     MA_REQUIRE(ctx && flow && keep, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
     MA_REQUIRE(H >= 1 && W >= 1 && H <= FS_SIDE_MAX && W <= FS_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_REQUIRE(margin >= 0 && margin <= MA_FOLD_MASK_MAX_MARGIN, "margin must be in [0, 32]");
     const int nbx1 = (W + 255) / 256, nbx2 = (W + FM_TW - 1) / FM_TW;

@@ -121,7 +121,8 @@ extern "C" int ma_landmark_flow(ma_ctx* ctx, const double* cw, int n, const doub
     MA_REQUIRE(H >= 1 && W >= 1 && H <= LM_SIDE_MAX && W <= LM_SIDE_MAX, "flow sides must be in [1, 2^24]");
     MA_REQUIRE(stride >= 1, "the stride must be at least 1");
     MA_REQUIRE(finite_spline(a6, cx, cy, k), "the affine part, the centre and the scale must be finite");
-    MA_REQUIRE(((uintptr_t)cw & 31) == 0, "cw must be 32-byte aligned");
+    MA_REQUIRE_ALIGNED(cw, 32, "cw");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     Mat6 A;
     for (int i = 0; i < 6; i++) A.v[i] = a6[i];
     const int gh = grid_nodes(H, stride), gw = grid_nodes(W, stride);
@@ -141,7 +142,9 @@ extern "C" int ma_landmark_points(ma_ctx* ctx, const double* cw, int n, const do
     MA_REQUIRE(n >= 0 && n <= MA_LANDMARK_MAX, "the number of landmarks must be in [0, 2^20]");
     MA_REQUIRE(m >= 0, "the number of points must not be negative");
     MA_REQUIRE(finite_spline(a6, cx, cy, k), "the affine part, the centre and the scale must be finite");
-    MA_REQUIRE(((uintptr_t)cw & 31) == 0, "cw must be 32-byte aligned");
+    MA_REQUIRE_ALIGNED(cw, 32, "cw");
+    MA_REQUIRE_ALIGNED(pts, 16, "pts");
+    MA_REQUIRE_ALIGNED(out, 16, "out");
     if (m == 0) return MA_OK;
     Mat6 A;
     for (int i = 0; i < 6; i++) A.v[i] = a6[i];

@@ -36,6 +36,18 @@ struct MaStageRing;   // ring of page-locked chunks for staged transfers of page
         }                                                  \
     } while (0)
 
+// The alignment rule of include/microaligner_hip.h ("Device pointers"): every pointer argument that a kernel reads or writes
+// through a wider type than it is declared with -- pairs of floats as float2, pairs of doubles as double2, and the few
+// arguments a header gives a stricter figure for -- is checked here, on the host, before anything is launched or opened.
+// NULL passes: whether an argument may be NULL is another check.
+#define MA_REQUIRE_ALIGNED(ptr, bytes, name)                                                      \
+    do {                                                                                          \
+        if ((uintptr_t)(ptr) % (uintptr_t)(bytes) != 0) {                                         \
+            ma_set_error("invalid argument: %s must be %d-byte aligned", name, (int)(bytes));     \
+            return MA_EINVAL;                                                                     \
+        }                                                                                         \
+    } while (0)
+
 #define MA_TRY(expr)            \
     do {                        \
         int _rc = (expr);       \

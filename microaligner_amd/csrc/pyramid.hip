@@ -246,9 +246,10 @@ int ma_pyr_up_flow(ma_ctx* ctx, const float* src, int h, int w, float scale, flo
     MA_REQUIRE(h > 0 && w > 0 && dh > 0 && dw > 0 && (dh + 1) / 2 <= MA_GRID_Y_MAX * PU_ROWS, "bad size");
     MA_REQUIRE(abs(dw - w * 2) == dw % 2 && abs(dh - h * 2) == dh % 2,
                "cv2.pyrUp requires |dst - 2*src| == dst % 2 on both axes");
+    MA_REQUIRE_ALIGNED(src, 8, "src");
+    MA_REQUIRE_ALIGNED(dst, 16, "dst");
     MA_HIP(hipSetDevice(ctx->device));
     MaProfScope ps(ctx, MA_K_PYR_UP, (double)dh * dw);
-    MA_REQUIRE((size_t)dst % 16 == 0, "dst must be 16-byte aligned");
     hipLaunchKernelGGL(pyr_up_flow_kernel, dim3(((dw + 1) / 2 + 255) / 256, ((dh + 1) / 2 + PU_ROWS - 1) / PU_ROWS), dim3(256), 0, ctx->stream,
                        (const float2*)src, h, w, scale, (float2*)dst, dh, dw);
     MA_HIP(hipGetLastError());

@@ -317,7 +317,7 @@ int ma_qc_flow_grid(ma_ctx* ctx, const float* flow, int h, int w, int cell_h, in
     MaCellGrid g;
     long long ncells;
     MA_TRY(ma_cell_grid(h, w, cell_h, cell_w, &g, &ncells));
-    MA_REQUIRE(((size_t)flow & 7) == 0, "flow must be 8-byte aligned");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
     const int ntx = (g.cw + QF_TW - 1) / QF_TW;
     const long long ntiles = (long long)ntx * ((g.ch + QF_TH - 1) / QF_TH);
     MA_REQUIRE(ntiles <= 0x7fffffff, "cell too large");

@@ -209,6 +209,7 @@ int ma_optflow_register(ma_ctx* ctx, const void* ref, const void* mov, int dtype
                         float* flow_out, ma_level_report* reports, int max_reports, int* n_reports)
 {
     MA_REQUIRE(ctx && ref && mov && params && flow_out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow_out, 16, "flow_out");   // the last level ends in ma_pyr_up_flow's 16-byte stores into it
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
     MA_REQUIRE(H > 0 && W > 0, "image must be non-empty");
     const ma_params p = *params;

@@ -431,6 +431,7 @@ int ma_remap_bilinear(ma_ctx* ctx, const void* src, int dtype, int cn, int sh, i
                       int dw, void* dst)
 {
     MA_REQUIRE(ctx && src && map_xy && dst, "NULL argument");
+    MA_REQUIRE_ALIGNED(map_xy, 8, "map_xy");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
     MA_REQUIRE(cn == 1 || cn == 2, "cn must be 1 or 2");
     MA_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "empty image");
@@ -481,6 +482,7 @@ static int warp_tiled_impl(ma_ctx* ctx, const void* img, int dtype, int H, int W
                            void* out, float* minmax_dev, unsigned* flow_cellkeys_dev = nullptr)
 {
     MA_REQUIRE(ctx && img && flow && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
     MA_REQUIRE(H > 0 && W > 0, "bad image size");
     MA_REQUIRE(H <= MA_GRID_Y_MAX * WARP_ROWS, "image too tall");
@@ -561,6 +563,7 @@ int ma_warp_pages_host(ma_ctx* ctx, const void* const* pages_host, void* const* 
                        int H, int W, const float* flow, int tile, int overlap)
 {
     MA_REQUIRE(ctx && pages_host && out_host && flow, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
     MA_REQUIRE(H > 0 && W > 0 && H <= MA_GRID_Y_MAX * WARP_ROWS && n_pages >= 0, "bad size");
     MA_REQUIRE(tile >= 0 && overlap >= 0, "tile/overlap must be >= 0");
@@ -590,6 +593,9 @@ int ma_merge_flows_tiled(ma_ctx* ctx, const float* flow1, const float* flow2, in
                          float* out)
 {
     MA_REQUIRE(ctx && flow1 && flow2 && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow1, 8, "flow1");
+    MA_REQUIRE_ALIGNED(flow2, 8, "flow2");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     MA_REQUIRE(H > 0 && W > 0 && H <= MA_GRID_Y_MAX * MERGE_ROWS, "bad image size");
     MA_REQUIRE(tile >= 0 && overlap >= 0, "tile/overlap must be >= 0");
     MaTiling g = ma_make_tiling(H, W, tile, overlap);
@@ -624,6 +630,9 @@ int ma_merge_flows_tiled_cells(ma_ctx* ctx, const float* flow1, const float* flo
                                const unsigned* cellkeys1, const unsigned* cellkeys2, float* out)
 {
     MA_REQUIRE(ctx && flow1 && flow2 && out && cellkeys1 && cellkeys2, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow1, 8, "flow1");
+    MA_REQUIRE_ALIGNED(flow2, 8, "flow2");
+    MA_REQUIRE_ALIGNED(out, 8, "out");
     MA_REQUIRE(H > 0 && W > 0 && H <= MA_GRID_Y_MAX * MERGE_ROWS, "bad image size");
     MA_REQUIRE(tile > 2 * overlap && overlap > 0, "flow cell maxima need tile > 2*overlap > 0");
     MaTiling g = ma_make_tiling(H, W, tile, overlap);

@@ -211,6 +211,7 @@ int ma_remap_interp(ma_ctx* ctx, const void* src, int dtype, int cn, int sh, int
     MA_REQUIRE(interp_known(interp), "interp must be MA_INTER_NEAREST, _LINEAR, _CUBIC or _LANCZOS4");
     if (interp == MA_INTER_LINEAR) return ma_remap_bilinear(ctx, src, dtype, cn, sh, sw, map_xy, dh, dw, dst);
     MA_REQUIRE(ctx && src && map_xy && dst, "NULL argument");
+    MA_REQUIRE_ALIGNED(map_xy, 8, "map_xy");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
     MA_REQUIRE(cn >= 1 && cn <= 4, "cn must be 1 to 4");
     MA_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "empty image");
@@ -240,6 +241,7 @@ int ma_warp_tiled_interp(ma_ctx* ctx, const void* img, int dtype, int H, int W, 
     MA_REQUIRE(interp_known(interp), "interp must be MA_INTER_NEAREST, _LINEAR, _CUBIC or _LANCZOS4");
     if (interp == MA_INTER_LINEAR) return ma_warp_tiled(ctx, img, dtype, H, W, flow, tile, overlap, out);
     MA_REQUIRE(ctx && img && flow && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
     MA_REQUIRE(H > 0 && W > 0, "bad image size");
     MA_REQUIRE(tile >= 0 && overlap >= 0, "tile/overlap must be >= 0");
@@ -259,6 +261,7 @@ int ma_warp_pages_host_interp(ma_ctx* ctx, const void* const* pages_host, void* 
     MA_REQUIRE(interp_known(interp), "interp must be MA_INTER_NEAREST, _LINEAR, _CUBIC or _LANCZOS4");
     if (interp == MA_INTER_LINEAR) return ma_warp_pages_host(ctx, pages_host, out_host, n_pages, dtype, H, W, flow, tile, overlap);
     MA_REQUIRE(ctx && pages_host && out_host && flow, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
     MA_REQUIRE(dtype == MA_U8 || dtype == MA_U16 || dtype == MA_F32, "dtype must be u8/u16/f32");
     MA_REQUIRE(n_pages >= 0, "bad page count");
     long long band_bytes = 0;

@@ -253,6 +253,7 @@ int ma_warp_affine_flow(ma_ctx* ctx, const void* img, int dtype, int h, int w, i
 {
     MA_TRY(check_args(dtype, h, w, pad_left, pad_top, H, W, m, interp));
     MA_REQUIRE(ctx && img && flow && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
     MA_HIP(hipSetDevice(ctx->device));
     MA_TRY(ensure_tables(ctx));
     MaProfScope ps(ctx, MA_K_OTHER, (double)H * W);
@@ -265,6 +266,7 @@ int ma_warp_affine_grid(ma_ctx* ctx, const void* img, int dtype, int h, int w, i
 {
     MA_TRY(check_args(dtype, h, w, pad_left, pad_top, H, W, m, interp));
     MA_REQUIRE(ctx && img && nodes && out, "NULL argument");
+    MA_REQUIRE_ALIGNED(nodes, 8, "nodes");
     MA_REQUIRE(s >= 1, "the stride must be at least 1");
     MA_HIP(hipSetDevice(ctx->device));
     MA_TRY(ensure_tables(ctx));
@@ -317,6 +319,7 @@ int ma_warp_affine_flow_pages_host(ma_ctx* ctx, const void* const* pages_host, v
                                    const double m[6], int interp)
 {
     MA_REQUIRE(flow, "NULL argument");
+    MA_REQUIRE_ALIGNED(flow, 8, "flow");
     return compose_pages(ctx, pages_host, out_host, n_pages, dtype, h, w, pad_left, pad_top, DenseFlow{(const float2*)flow}, H,
                          W, m, interp);
 }
@@ -326,6 +329,7 @@ int ma_warp_affine_grid_pages_host(ma_ctx* ctx, const void* const* pages_host, v
                                    int s, const double m[6], int interp)
 {
     MA_REQUIRE(nodes, "NULL argument");
+    MA_REQUIRE_ALIGNED(nodes, 8, "nodes");
     MA_REQUIRE(s >= 1, "the stride must be at least 1");
     MA_REQUIRE(H > 0 && W > 0, "empty image");
     return compose_pages(ctx, pages_host, out_host, n_pages, dtype, h, w, pad_left, pad_top,

@@ -307,5 +307,5 @@ def test_c_entries_refuse_bad_arguments_without_launching(ctx):
 
 def test_the_loaded_library_is_this_trees():
     from microaligner_amd import build
-    assert _lib.source_hash() == build.source_hash() == "7f5e1df0cf7595ec"
+    assert _lib.source_hash() == build.source_hash() == "19a3cec2ac2dae56"
     assert hasattr(_lib.load(), "ma_landmark_flow") and hasattr(_lib.load(), "ma_landmark_points")
