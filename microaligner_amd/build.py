@@ -17,44 +17,48 @@ LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
            "flow_compose.hip", "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip", "texture.hip", "direct_affine.hip", "flow_refine.hip",
            "landmarks.hip", "translation.hip", "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip", "debug_fill.hip"]
+
+
+def _inc(name):
+    """a public header"""
+    return os.path.join(HERE, "..", "include", name)
+
+
 HEADERS = [os.path.join(CSRC, "ma_internal.h"), os.path.join(CSRC, "remap_common.h"), os.path.join(CSRC, "nmi_score.h"),
-           os.path.join(HERE, "..", "include", "microaligner_hip.h")]
+           _inc("microaligner_hip.h")]
 # headers of single sources that are off the measured path (not in HEADERS, so not in source_hash())
-_INTERP_HEADERS = [os.path.join(HERE, "..", "include", "microaligner_interp.h"), os.path.join(CSRC, "remap_interp.h")]
+_SMOOTH_H = _inc("microaligner_flowsmooth.h")            # the weight kinds, for the sources that take a weight
+_INTERP_HEADERS = [_inc("microaligner_interp.h"), os.path.join(CSRC, "remap_interp.h")]
 _CELL_GRID = os.path.join(CSRC, "cell_grid.h")
-_FLOW_GRID = [os.path.join(HERE, "..", "include", "microaligner_flowgrid.h"), os.path.join(CSRC, "flow_grid_eval.h")]
+_FLOW_GRID = [_inc("microaligner_flowgrid.h"), os.path.join(CSRC, "flow_grid_eval.h")]
 _FLOW_JACOBIAN = os.path.join(CSRC, "flow_jacobian.h")   # det J, stated once for the quality maps and the fold mask
 # the separable FIR tile of the smoothing, the texture maps, the refinement and the local correlation maps
 _WINDOW_FIR = os.path.join(CSRC, "window_fir.h")
 # the weight argument of the seven calls that take one: its readers on the device, its check and dispatch at the C entry
 _WEIGHT_MAP = os.path.join(CSRC, "weight_map.h")
-SOURCE_HEADERS = {"qc.hip": [os.path.join(HERE, "..", "include", "microaligner_qc.h"), _CELL_GRID, _FLOW_JACOBIAN],
+# the per-call event counts: the wave tally of the kernels, the counters of the ctx workspace and their read-back
+_CALL_COUNTS = os.path.join(CSRC, "call_counts.h")
+# the fixed-order float64 reduction of the moment sums and their scatter into the caller's arrays
+_MOMENT_SUMS = os.path.join(CSRC, "moment_sums.h")
+SOURCE_HEADERS = {"qc.hip": [_inc("microaligner_qc.h"), _CELL_GRID, _FLOW_JACOBIAN],
                   "remap_interp.hip": _INTERP_HEADERS,
-                  "warp_compose.hip": _INTERP_HEADERS + [os.path.join(HERE, "..", "include", "microaligner_compose.h")],
-                  "flow_compose.hip": [os.path.join(HERE, "..", "include", "microaligner_flowcompose.h")],
-                  "flow_invert.hip": [os.path.join(HERE, "..", "include", "microaligner_flowinvert.h")],
-                  "residual_shift.hip": [os.path.join(HERE, "..", "include", "microaligner_residual.h"), _CELL_GRID],
+                  "warp_compose.hip": _INTERP_HEADERS + [_inc("microaligner_compose.h")],
+                  "flow_compose.hip": [_inc("microaligner_flowcompose.h")],
+                  "flow_invert.hip": [_inc("microaligner_flowinvert.h"), _CALL_COUNTS],
+                  "residual_shift.hip": [_inc("microaligner_residual.h"), _CELL_GRID],
                   "flow_grid.hip": _FLOW_GRID + [_CELL_GRID],
-                  "flow_smooth.hip": [os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID, _FLOW_JACOBIAN,
-                                      _WINDOW_FIR, _WEIGHT_MAP],
-                  "flow_affine.hip": [os.path.join(HERE, "..", "include", "microaligner_flowaffine.h"),
-                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID, _WEIGHT_MAP],
-                  "texture.hip": [os.path.join(HERE, "..", "include", "microaligner_texture.h"), _CELL_GRID, _WINDOW_FIR],
-                  "direct_affine.hip": [os.path.join(HERE, "..", "include", "microaligner_direct.h"),
-                                        os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP],
-                  "flow_refine.hip": [os.path.join(HERE, "..", "include", "microaligner_flowrefine.h"),
-                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WINDOW_FIR, _WEIGHT_MAP],
-                  "landmarks.hip": [os.path.join(HERE, "..", "include", "microaligner_landmarks.h")],
-                  "translation.hip": [os.path.join(HERE, "..", "include", "microaligner_translation.h")],
-                  "quantile.hip": [os.path.join(HERE, "..", "include", "microaligner_quantile.h")],
-                  "local_correlation.hip": [os.path.join(HERE, "..", "include", "microaligner_localcorr.h"),
-                                            os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _CELL_GRID,
-                                            _WINDOW_FIR, _WEIGHT_MAP],
-                  "flow_median.hip": [os.path.join(HERE, "..", "include", "microaligner_flowmedian.h"),
-                                      os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP],
-                  "flow_fill.hip": [os.path.join(HERE, "..", "include", "microaligner_flowfill.h"),
-                                    os.path.join(HERE, "..", "include", "microaligner_flowsmooth.h"), _WEIGHT_MAP],
-                  "debug_fill.hip": [os.path.join(HERE, "..", "include", "microaligner_debug.h")]}
+                  "flow_smooth.hip": [_SMOOTH_H, _CELL_GRID, _FLOW_JACOBIAN, _WINDOW_FIR, _WEIGHT_MAP, _CALL_COUNTS],
+                  "flow_affine.hip": [_inc("microaligner_flowaffine.h"), _SMOOTH_H, _CELL_GRID, _WEIGHT_MAP, _MOMENT_SUMS],
+                  "texture.hip": [_inc("microaligner_texture.h"), _CELL_GRID, _WINDOW_FIR],
+                  "direct_affine.hip": [_inc("microaligner_direct.h"), _SMOOTH_H, _WEIGHT_MAP, _CELL_GRID, _MOMENT_SUMS],
+                  "flow_refine.hip": [_inc("microaligner_flowrefine.h"), _SMOOTH_H, _WINDOW_FIR, _WEIGHT_MAP, _CALL_COUNTS],
+                  "landmarks.hip": [_inc("microaligner_landmarks.h")],
+                  "translation.hip": [_inc("microaligner_translation.h")],
+                  "quantile.hip": [_inc("microaligner_quantile.h")],
+                  "local_correlation.hip": [_inc("microaligner_localcorr.h"), _SMOOTH_H, _CELL_GRID, _WINDOW_FIR, _WEIGHT_MAP],
+                  "flow_median.hip": [_inc("microaligner_flowmedian.h"), _SMOOTH_H, _WEIGHT_MAP, _CALL_COUNTS],
+                  "flow_fill.hip": [_inc("microaligner_flowfill.h"), _SMOOTH_H, _WEIGHT_MAP, _CALL_COUNTS],
+                  "debug_fill.hip": [_inc("microaligner_debug.h")]}
 # the grid-flow headers are also read by the two sources whose kernels take their flow from a grid: further dependencies of
 # those sources, beside the headers of their own above
 GRID_FLOW_USERS = {"warp_compose.hip": _FLOW_GRID, "flow_invert.hip": _FLOW_GRID}
@@ -122,8 +126,9 @@ def source_hash():
     #   - the test hook that fills a context's idle scratch memory, which only tests call and which launches no kernel;
     #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps, flow_jacobian.h, det J of
     #     the quality maps and the fold mask, window_fir.h, the separable FIR tile of the flow smoothing, the texture
-    #     maps, the flow refinement and the local correlation maps, and weight_map.h, the weight argument of the seven
-    #     calls above that take one (SOURCE_HEADERS).
+    #     maps, the flow refinement and the local correlation maps, weight_map.h, the weight argument of the seven
+    #     calls above that take one, call_counts.h, the per-call event counts of the flow calls above that return some,
+    #     and moment_sums.h, the fixed-order float64 reduction of the two kinds of affine moments (SOURCE_HEADERS).
     off_path = {"probe.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "affine.hip", "qc.hip",
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
                 "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip",

@@ -5,10 +5,12 @@
 // columns x DA_TH rows and walks down it row by row, a lane owns one column, so the reference (and the weight) is read
 // coalesced and the four taps of a wave's row are gathers that stay within a few rows of the moving image for a small
 // rotation.  The gradient is that of the bilinear interpolant itself: no neighbours, no LDS tile.  The 31 sums and 5 counts
-// stay in registers (float64, every operation its own rounding), are combined over the block in a fixed tree (lanes by
-// shuffles, then the waves in order) and written as the tile's partial; da_final_kernel adds the partials in a fixed order.
-// No floating-point atomics: two calls give the same bits.
+// stay in registers (float64, every operation its own rounding), are combined over the block and written as the tile's
+// partial; da_final_kernel adds the partials.  Both in the fixed order of moment_sums.h: two calls give the same bits.  The
+// host side is the batch loop of cell_grid.h with the image as its one cell.
 #include "../../include/microaligner_direct.h"
+#include "cell_grid.h"
+#include "moment_sums.h"
 #include "weight_map.h"
 
 #include <cmath>
@@ -33,29 +35,6 @@ template <typename T>
 __device__ __forceinline__ bool da_finite(T) { return true; }
 template <>
 __device__ __forceinline__ bool da_finite<float>(float v) { return fabsf(v) < INFINITY; }
-
-// The block's total of v in a fixed order: the lanes of a wave by a shuffle tree, then the waves 0, 1, ... in sequence.
-// Valid in thread 0.  red: one DaPart per wave.
-__device__ __forceinline__ DaPart da_block_combine(DaPart* red, DaPart v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < DA_NS; k++) v.s[k] = __dadd_rn(v.s[k], __shfl_down(v.s[k], off, 64));
-#pragma unroll
-        for (int k = 0; k < DA_NC; k++) v.c[k] += __shfl_down(v.c[k], off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int wv = 1; wv < DA_T / 64; wv++) {
-#pragma unroll
-            for (int k = 0; k < DA_NS; k++) v.s[k] = __dadd_rn(v.s[k], red[wv].s[k]);
-#pragma unroll
-            for (int k = 0; k < DA_NC; k++) v.c[k] += red[wv].c[k];
-        }
-    return v;
-}
 
 // counts: used, outside, invalid, unweighted, trimmed
 enum { DA_USED = 0, DA_OUTSIDE = 1, DA_INVALID = 2, DA_UNWEIGHTED = 3, DA_TRIMMED = 4 };
@@ -157,7 +136,7 @@ __global__ __launch_bounds__(DA_T) void da_tile_kernel(const TR* __restrict__ re
     for (int k = 0; k < DA_NS; k++) v.s[k] = s[k];
 #pragma unroll
     for (int k = 0; k < DA_NC; k++) v.c[k] = cnt[k];
-    v = da_block_combine(red, v);
+    v = d_moments_block<DA_T>(red, v);
     if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
 
@@ -173,7 +152,7 @@ __global__ __launch_bounds__(DA_T) void da_final_kernel(const DaPart* __restrict
 #pragma unroll
         for (int k = 0; k < DA_NC; k++) v.c[k] += p.c[k];
     }
-    v = da_block_combine(red, v);
+    v = d_moments_block<DA_T>(red, v);
     if (threadIdx.x == 0) *res = v;
 }
 
@@ -220,33 +199,27 @@ extern "C" int ma_direct_affine_moments(ma_ctx* ctx, const void* ref, int ref_dt
     a.ntx = (W + DA_TW - 1) / DA_TW;
     const long long ntiles = (long long)a.ntx * ((H + DA_TH - 1) / DA_TH);
     MA_REQUIRE(ntiles <= 0x7fffffff, "image too large");
-    const size_t ws_bytes = (size_t)(ntiles + 1) * sizeof(DaPart);
-    if (ws_bytes > ctx->ws_limit) {
-        ma_set_error("workspace limit %zu is below the %zu bytes the tiles' partial sums take", ctx->ws_limit, ws_bytes);
-        return MA_ENOMEM;
-    }
-    MA_HIP(hipSetDevice(ctx->device));
-    MA_TRY(ma_ws_reserve(ctx, ws_bytes));
-    MA_TRY(ma_pinned_reserve(ctx, sizeof(DaPart)));
-    DaPart* part = (DaPart*)ctx->ws;
-    DaPart* res = part + ntiles;
-    {
-        MaProfScope ps(ctx, MA_K_OTHER, (double)H * W);
-        switch (ref_dtype) {
-        case MA_U8: da_launch<unsigned char>(ctx, ref, mov, mov_dtype, weight, a, (unsigned)ntiles, part); break;
-        case MA_U16: da_launch<unsigned short>(ctx, ref, mov, mov_dtype, weight, a, (unsigned)ntiles, part); break;
-        default: da_launch<float>(ctx, ref, mov, mov_dtype, weight, a, (unsigned)ntiles, part); break;
-        }
-        hipLaunchKernelGGL(da_final_kernel, dim3(1), dim3(DA_T), 0, ctx->stream, (const DaPart*)part, (int)ntiles, res);
-        MA_HIP(hipGetLastError());
-    }
-    MA_HIP(hipMemcpyAsync(ctx->pinned, res, sizeof(DaPart), hipMemcpyDeviceToHost, ctx->stream));
-    MA_HIP(hipStreamSynchronize(ctx->stream));
-    const DaPart* r = (const DaPart*)ctx->pinned;
-    for (int k = 0; k < DA_NS; k++) sums_host[k] = r->s[k];
-    for (int k = 0; k < DA_NC; k++) counts_host[k] = (long long)r->c[k];
-    if (ctx->profile) MA_TRY(ma_profile_flush(ctx));
-    return MA_OK;
+    // the whole image is one cell: the tiles' partials and, behind them, the result
+    return ma_cell_batches(
+        ctx, 1, (size_t)(ntiles + 1) * sizeof(DaPart), sizeof(DaPart), 1,
+        [&](long long, unsigned, const void** dev, size_t* bytes) -> int {
+            DaPart* part = (DaPart*)ctx->ws;
+            DaPart* res = part + ntiles;
+            MaProfScope ps(ctx, MA_K_OTHER, (double)H * W);
+            switch (ref_dtype) {
+            case MA_U8: da_launch<unsigned char>(ctx, ref, mov, mov_dtype, weight, a, (unsigned)ntiles, part); break;
+            case MA_U16: da_launch<unsigned short>(ctx, ref, mov, mov_dtype, weight, a, (unsigned)ntiles, part); break;
+            default: da_launch<float>(ctx, ref, mov, mov_dtype, weight, a, (unsigned)ntiles, part); break;
+            }
+            hipLaunchKernelGGL(da_final_kernel, dim3(1), dim3(DA_T), 0, ctx->stream, (const DaPart*)part, (int)ntiles, res);
+            MA_HIP(hipGetLastError());
+            *dev = res;
+            *bytes = sizeof(DaPart);
+            return MA_OK;
+        },
+        [&](long long c0, unsigned nb, const void* pinned) {
+            ma_moments_scatter((const DaPart*)pinned, c0, nb, sums_host, counts_host);
+        });
 }
 
 extern "C" int ma_direct_mask_weight(ma_ctx* ctx, const unsigned char* mask, size_t n, float* out)

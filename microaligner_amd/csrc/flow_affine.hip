@@ -6,12 +6,12 @@
 // the flow's memory per row (the pair index is that of the memory, not of the tile, so the load is aligned whatever the
 // row's start) and loads it whole where the pair lies inside the row's span, pixel by pixel (8 B) at its ends.  FA_TW = 510:
 // any span of 510 pixels touches at most 256 pairs.  The 14 sums and 4 counts stay in registers (float64, every operation
-// its own rounding), are combined over the block in a fixed tree (lanes by shuffles, then the waves in order) and written
-// as the tile's partial; fa_cell_kernel adds the partials of a cell in a fixed order.  No floating-point atomics: two calls
-// give the same bits.
+// its own rounding), are combined over the block and written as the tile's partial; fa_cell_kernel adds the partials of a
+// cell.  Both in the fixed order of moment_sums.h: two calls give the same bits.
 // Apply: pointwise, 8 B in and 8 B out per pixel.
 #include "../../include/microaligner_flowaffine.h"
 #include "cell_grid.h"
+#include "moment_sums.h"
 #include "weight_map.h"
 
 #include <cmath>
@@ -69,30 +69,6 @@ __device__ __forceinline__ void fa_pixel(FaAcc& acc, int x, int y, double cx, do
     for (int k = 0; k < FA_NS; k++) acc.s[k] = __dadd_rn(acc.s[k], t[k]);
 }
 
-// The block's total of v in a fixed order: the lanes of a wave by a shuffle tree, then the waves 0, 1, ... in sequence.
-// Valid in thread 0.  red: one FaPart per wave.
-template <int NT>
-__device__ __forceinline__ FaPart fa_block_combine(FaPart* red, FaPart v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < FA_NS; k++) v.s[k] = __dadd_rn(v.s[k], __shfl_down(v.s[k], off, 64));
-#pragma unroll
-        for (int k = 0; k < FA_NC; k++) v.c[k] += __shfl_down(v.c[k], off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int wv = 1; wv < NT / 64; wv++) {
-#pragma unroll
-            for (int k = 0; k < FA_NS; k++) v.s[k] = __dadd_rn(v.s[k], red[wv].s[k]);
-#pragma unroll
-            for (int k = 0; k < FA_NC; k++) v.c[k] += red[wv].c[k];
-        }
-    return v;
-}
-
 template <int KIND, bool TRIM>
 __global__ __launch_bounds__(FA_T) void fa_tile_kernel(const float* __restrict__ flow, MaCellGrid g, const void* __restrict__ weight,
                                                        int ntx, int ntiles, int vec_ok, FaPrior pr, FaPart* __restrict__ part)
@@ -135,7 +111,7 @@ __global__ __launch_bounds__(FA_T) void fa_tile_kernel(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < FA_NS; k++) v.s[k] = acc.s[k];
     v.c[0] = acc.used; v.c[1] = acc.invalid; v.c[2] = acc.unweighted; v.c[3] = acc.trimmed;
-    v = fa_block_combine<FA_T>(red, v);
+    v = d_moments_block<FA_T>(red, v);
     if (threadIdx.x == 0) *out = v;
 }
 
@@ -151,7 +127,7 @@ __global__ __launch_bounds__(FA_T) void fa_cell_kernel(const FaPart* __restrict_
 #pragma unroll
         for (int k = 0; k < FA_NC; k++) v.c[k] += p.c[k];
     }
-    v = fa_block_combine<FA_T>(red, v);
+    v = d_moments_block<FA_T>(red, v);
     if (threadIdx.x == 0) res[blockIdx.x] = v;
 }
 
@@ -227,11 +203,7 @@ extern "C" int ma_flow_affine_moments(ma_ctx* ctx, const float* flow, int H, int
             return MA_OK;
         },
         [&](long long c0, unsigned nb, const void* pinned) {
-            const FaPart* r = (const FaPart*)pinned;
-            for (unsigned i = 0; i < nb; i++) {
-                for (int k = 0; k < FA_NS; k++) sums_host[(size_t)(c0 + i) * FA_NS + k] = r[i].s[k];
-                for (int k = 0; k < FA_NC; k++) counts_host[(size_t)(c0 + i) * FA_NC + k] = (long long)r[i].c[k];
-            }
+            ma_moments_scatter((const FaPart*)pinned, c0, nb, sums_host, counts_host);
         });
 }
 

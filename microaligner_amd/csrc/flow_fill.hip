@@ -12,10 +12,10 @@
 //   - ff_pull       : the quad of level l -> the entry of level l + 1;
 //   - ff_push       : the 3 x 3 neighbourhood of the parent in G_{l+1} serves the four outputs of the quad: three rows of
 //                     two row interpolations each, then four column interpolations, then the blend with (a, t) of level l;
-//   - ff_push0<KIND>: the same over the flow and the weight, out, and the three counts (one integer atomic per wave and
-//                     count).
+//   - ff_push0<KIND>: the same over the flow and the weight, out, and the three counts (call_counts.h).
 // The pull that makes the 1 x 1 level applies the header's "top" rule (NaN where nothing was kept).  No LDS, no scratch.
 #include "../../include/microaligner_flowfill.h"
+#include "call_counts.h"
 #include "weight_map.h"
 
 #include <cmath>
@@ -190,19 +190,7 @@ __global__ __launch_bounds__(256) void ff_push0(const float2* flow, int H, int W
                 }
             }
     }
-    if (counts) {     // wave-uniform; integer adds, one per wave and count, so the totals do not depend on the order
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            dropped += __shfl_down(dropped, off, 64);
-            blended += __shfl_down(blended, off, 64);
-            unsupported += __shfl_down(unsupported, off, 64);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            if (dropped) atomicAdd(counts, (unsigned long long)dropped);
-            if (blended) atomicAdd(counts + 1, (unsigned long long)blended);
-            if (unsupported) atomicAdd(counts + 2, (unsigned long long)unsupported);
-        }
-    }
+    if (counts) d_wave_tally(counts, {dropped, blended, unsupported});     // wave-uniform
 }
 
 // the blocks of a launch over hc x wc parents
@@ -239,12 +227,8 @@ extern "C" int ma_fill_flow(ma_ctx* ctx, const float* flow, int H, int W, const 
                "flow too large: more than 2^31 - 1 tiles of 8 x 128 pixels");
     MA_HIP(hipSetDevice(ctx->device));
     MA_TRY(ma_ws_reserve(ctx, FF_LEVELS_AT + at[L + 1] * sizeof(float4)));
-    unsigned long long* counts = nullptr;
-    if (counts_host) {
-        MA_TRY(ma_pinned_reserve(ctx, 3 * sizeof(unsigned long long)));
-        counts = (unsigned long long*)ctx->ws;
-        MA_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), ctx->stream));
-    }
+    unsigned long long* counts;
+    MA_TRY(ma_call_counts(ctx, counts_host != nullptr, 3, &counts));      // behind the reserve of the levels: ctx->ws is final
     float4* levels = (float4*)((char*)ctx->ws + FF_LEVELS_AT);
     auto level = [&](int l) { return levels + at[l]; };
     const MaWeight wt = ma_weight_map(weight, weight_kind, W, cell_h, cell_w);
@@ -275,10 +259,6 @@ extern "C" int ma_fill_flow(ma_ctx* ctx, const float* flow, int H, int W, const 
         });
     }
     MA_HIP(hipGetLastError());
-    if (counts_host) {
-        MA_HIP(hipMemcpyAsync(ctx->pinned, counts, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        MA_HIP(hipStreamSynchronize(ctx->stream));
-        for (int k = 0; k < 3; k++) counts_host[k] = (long long)((const unsigned long long*)ctx->pinned)[k];
-    }
+    if (counts_host) MA_TRY(ma_read_call_counts(ctx, counts, 3, counts_host));
     return MA_OK;
 }

@@ -5,9 +5,11 @@
 // compose_flows_kernel (flow_compose.hip): one column per lane, FI_ROWS rows per thread; the sampler is the unquantised
 // bilinear one of the header, not remap_common.h's.  Per pixel one 8-byte write (plus 4 for the residual) and four
 // gathered float2 taps per step; the taps of a step lie within |g| px of the pixel, so neighbouring lanes share their
-// cache lines.  Lanes finish at different steps: a wave runs until its last lane stops.
+// cache lines.  Lanes finish at different steps: a wave runs until its last lane stops.  The pixels that did not converge
+// are counted as call_counts.h states.
 #include "../../include/microaligner_flowinvert.h"
 #include "../../include/microaligner_flowgrid.h"
+#include "call_counts.h"
 #include "flow_grid_eval.h"
 #include "ma_internal.h"
 
@@ -104,11 +106,7 @@ __global__ __launch_bounds__(256) void invert_flow_kernel(const float2* __restri
             missed += live[r] ? 1u : 0u;
         }
     }
-    if (not_converged) {        // wave-uniform; one integer add per wave, so the total does not depend on the order
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) missed += __shfl_down(missed, off, 64);
-        if ((threadIdx.x & 63) == 0 && missed) atomicAdd(not_converged, (unsigned long long)missed);
-    }
+    if (not_converged) d_wave_tally(not_converged, {missed});        // wave-uniform
 }
 
 struct Mat6 { double v[6]; };
@@ -202,22 +200,13 @@ extern "C" int ma_invert_flow(ma_ctx* ctx, const float* flow, int H, int W, int 
     MA_REQUIRE(std::isfinite(tol) && tol >= 0.f, "tol must be finite and not negative");
     MA_REQUIRE(out != flow && residual != flow && (const float*)residual != out, "out, residual and flow must be distinct arrays");
     MA_HIP(hipSetDevice(ctx->device));
-    unsigned long long* counter = nullptr;
-    if (not_converged_host) {
-        MA_TRY(ma_ws_reserve(ctx, sizeof(unsigned long long)));
-        MA_TRY(ma_pinned_reserve(ctx, sizeof(unsigned long long)));
-        counter = (unsigned long long*)ctx->ws;
-        MA_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
-    }
+    unsigned long long* counter;
+    MA_TRY(ma_call_counts(ctx, not_converged_host != nullptr, 1, &counter));
     const int nby = (H + FI_ROWS - 1) / FI_ROWS;
     hipLaunchKernelGGL(invert_flow_kernel<FI_ROWS>, dim3((W + 255) / 256, nby < MA_GRID_Y_MAX ? nby : MA_GRID_Y_MAX), dim3(256),
                        0, ctx->stream, (const float2*)flow, H, W, nby, max_iter, tol, (float2*)out, residual, counter);
     MA_HIP(hipGetLastError());
-    if (not_converged_host) {
-        MA_HIP(hipMemcpyAsync(ctx->pinned, counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        MA_HIP(hipStreamSynchronize(ctx->stream));
-        *not_converged_host = (long long)*(const unsigned long long*)ctx->pinned;
-    }
+    if (not_converged_host) MA_TRY(ma_read_call_counts(ctx, counter, 1, not_converged_host));
     return MA_OK;
 }
 

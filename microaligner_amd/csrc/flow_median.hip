@@ -5,7 +5,7 @@
 // into LDS as the header's int32 keys, an (u, v) pair per pixel (coalesced float2 loads, the weight looked up beside them),
 // a sample that does not participate or lies outside the image as the marker MF_MARK in both components.  Lane = column,
 // a wave owns MF_TH / 4 rows; a thread selects both components of a pixel as two independent chains, then writes out, keep
-// and its share of the counts (one integer atomic per wave and count).  No scratch, no workspace but the counters.
+// and its share of the counts (call_counts.h).  No scratch, no workspace but the counters.
 //   - generic (R = 0), every r in 1 .. 7 and every n: one sweep of the window for n and the smallest and largest key, then
 //     bisection on the key between those two, counting the keys <= pivot over the window, until the smallest key with
 //     (n - 1) / 2 + 1 keys at or below it is left -- a key of the window, so the result is exact.  The marker is above
@@ -16,6 +16,7 @@
 // Both work on the integer keys: the result does not depend on how float min / max treat +-0 and denormals, and the
 // selection compiles to v_min_i32 / v_max_i32 / v_med3_i32.
 #include "../../include/microaligner_flowmedian.h"
+#include "call_counts.h"
 #include "weight_map.h"
 
 #include <climits>
@@ -217,19 +218,7 @@ __global__ __launch_bounds__(256) void mf_kernel(const float2* __restrict__ flow
         if (out) out[i] = o;
         if (keep) keep[i] = bad ? 0 : 1;
     }
-    if (counts) {     // wave-uniform; integer adds, one per wave and count, so the totals do not depend on the order
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            outliers += __shfl_down(outliers, off, 64);
-            dropped += __shfl_down(dropped, off, 64);
-            unsupported += __shfl_down(unsupported, off, 64);
-        }
-        if (lane == 0) {
-            if (outliers) atomicAdd(counts, (unsigned long long)outliers);
-            if (dropped) atomicAdd(counts + 1, (unsigned long long)dropped);
-            if (unsupported) atomicAdd(counts + 2, (unsigned long long)unsupported);
-        }
-    }
+    if (counts) d_wave_tally(counts, {outliers, dropped, unsupported});     // wave-uniform
 }
 
 template <int KIND, int R>
@@ -270,13 +259,8 @@ extern "C" int ma_median_flow(ma_ctx* ctx, const float* flow, int H, int W, int 
     const long long nbx = (W + MF_TW - 1) / MF_TW, nby = (H + MF_TH - 1) / MF_TH;
     MA_REQUIRE(nbx * nby <= 0x7fffffffLL, "flow too large: more than 2^31 - 1 tiles of 32 x 64 pixels");
     MA_HIP(hipSetDevice(ctx->device));
-    unsigned long long* counts = nullptr;
-    if (counts_host) {
-        MA_TRY(ma_ws_reserve(ctx, 3 * sizeof(unsigned long long)));
-        MA_TRY(ma_pinned_reserve(ctx, 3 * sizeof(unsigned long long)));
-        counts = (unsigned long long*)ctx->ws;
-        MA_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), ctx->stream));
-    }
+    unsigned long long* counts;
+    MA_TRY(ma_call_counts(ctx, counts_host != nullptr, 3, &counts));
     const MaWeight wt = ma_weight_map(weight, weight_kind, W, cell_h, cell_w);
     const bool generic = (flags & MA_MEDIAN_GENERIC) != 0 || r > MF_REG_MAX_RADIUS;
     const unsigned grid = (unsigned)(nbx * nby);
@@ -284,10 +268,6 @@ extern "C" int ma_median_flow(ma_ctx* ctx, const float* flow, int H, int W, int 
         mf_launch<kind()>(ctx, generic, grid, flow, H, W, wt, r, mode, thresh, (int)nbx, out, keep, counts);
     });
     MA_HIP(hipGetLastError());
-    if (counts_host) {
-        MA_HIP(hipMemcpyAsync(ctx->pinned, counts, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        MA_HIP(hipStreamSynchronize(ctx->stream));
-        for (int k = 0; k < 3; k++) counts_host[k] = (long long)((const unsigned long long*)ctx->pinned)[k];
-    }
+    if (counts_host) MA_TRY(ma_read_call_counts(ctx, counts, 3, counts_host));
     return MA_OK;
 }

@@ -9,9 +9,11 @@
 //     the reference; the weight kind is a wave-uniform branch.
 //   - The column pass keeps the five filtered planes in registers and ends in the solve, the clamp and the add: it reads and
 //     writes only the 8 B/px flow, and counts invalid and clamped pixels and the largest step with wave reductions, one
-//     integer atomic per wave and statistic.
+//     integer atomic per wave and statistic: the tally of call_counts.h with a maximum for its third value, so stated here;
+//     the host side of the statistics is that header's.
 // LDS is sized by r at launch (40 KiB at r = 12, 97 KiB at r = 128).
 #include "../../include/microaligner_flowrefine.h"
+#include "call_counts.h"
 #include "weight_map.h"
 #include "window_fir.h"
 
@@ -168,7 +170,7 @@ extern "C" int ma_flow_refine_step(ma_ctx* ctx, const void* ref, int dtype, cons
     MA_TRY(wf_taps(taps_host, r, &taps));
     MA_HIP(hipSetDevice(ctx->device));
     unsigned long long* stats;
-    MA_TRY(wf_counters(ctx, stats_host != nullptr, MA_REFINE_STATS, &stats));
+    MA_TRY(ma_call_counts(ctx, stats_host != nullptr, MA_REFINE_STATS, &stats));
     WfBuffers b;
     MA_TRY(wf_acquire(ctx, 0, FR_PLANES, H, W, 0, &b));
     hipLaunchKernelGGL(wf_setup_kernel<>, dim3(1), dim3(256), 0, ctx->stream, taps, r, b.aux);
@@ -179,6 +181,6 @@ extern "C" int ma_flow_refine_step(ma_ctx* ctx, const void* ref, int dtype, cons
     default: rc = fr_launch<float>(ctx, ref, warped, weight, weight_kind, H, W, r, b.aux, b.ws, floor, max_step, flow, out, stats); break;
     }
     MA_TRY(wf_finish(ctx, b, rc, nullptr));
-    if (stats_host) MA_TRY(wf_read_counters(ctx, stats, MA_REFINE_STATS, stats_host));
+    if (stats_host) MA_TRY(ma_read_call_counts(ctx, stats, MA_REFINE_STATS, stats_host));
     return MA_OK;
 }

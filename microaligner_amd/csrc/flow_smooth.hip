@@ -4,9 +4,10 @@
 // The smoothing is the separable window FIR of window_fir.h over the three planes w*u, w*v, w (a 12 B/px workspace).
 //   - The row pass stages the planes from the flow (float2 loads) and the weight, one plane after the other.
 //   - The column pass keeps the three filtered planes in registers and ends in the divide and the blend: it reads flow and
-//     weight again only for the blend, and counts the pixels without support, one integer atomic per wave.
+//     weight again only for the blend, and counts the pixels without support (call_counts.h, as the fold mask's kernels do).
 // LDS is sized by r at launch (43 KiB at r = 18, 97 KiB at r = 128).
 #include "../../include/microaligner_flowsmooth.h"
+#include "call_counts.h"
 #include "cell_grid.h"
 #include "flow_jacobian.h"
 #include "weight_map.h"
@@ -144,11 +145,7 @@ __global__ __launch_bounds__(64 * WF_NW) void fs_col_kernel(const float* __restr
         }
         out[i] = s;
     }
-    if (unsupported) {     // wave-uniform; one integer add per wave, so the total does not depend on the order
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) missed += __shfl_down(missed, off, 64);
-        if (lane == 0 && missed) atomicAdd(unsupported, (unsigned long long)missed);
-    }
+    if (unsupported) d_wave_tally(unsupported, {missed});     // wave-uniform
 }
 
 // ---- fold mask ------------------------------------------------------------------------------------------------------------
@@ -168,15 +165,7 @@ __global__ __launch_bounds__(256) void fs_bad_kernel(const float2* __restrict__ 
         invalid = !(d_finite(f.x) && d_finite(f.y));
         bad[i] = (folded | invalid) ? 1 : 0;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        folded += __shfl_down(folded, off, 64);
-        invalid += __shfl_down(invalid, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (folded) atomicAdd(counts, (unsigned long long)folded);
-        if (invalid) atomicAdd(counts + 1, (unsigned long long)invalid);
-    }
+    d_wave_tally(counts, {folded, invalid});
 }
 
 // keep = 1 - (bad dilated by the (2 margin + 1)^2 box), separably through LDS: the bad bytes of the tile and its margin,
@@ -213,9 +202,7 @@ __global__ __launch_bounds__(256) void fs_dilate_kernel(const unsigned char* __r
             dropped += any ? 1u : 0u;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) dropped += __shfl_down(dropped, off, 64);
-    if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(counts + 2, (unsigned long long)dropped);
+    d_wave_tally(counts + 2, {dropped});
 }
 
 template <int KIND>
@@ -256,7 +243,7 @@ extern "C" int ma_smooth_flow(ma_ctx* ctx, const float* flow, int H, int W, cons
     MA_TRY(wf_taps(taps_host, r, &taps));
     MA_HIP(hipSetDevice(ctx->device));
     unsigned long long* counter;
-    MA_TRY(wf_counters(ctx, unsupported_host != nullptr, 1, &counter));
+    MA_TRY(ma_call_counts(ctx, unsupported_host != nullptr, 1, &counter));
     const int ones = mode == MA_SMOOTH_BLEND ? 1 : 0;
     const size_t tail = ones ? (size_t)W + H : 0;
     WfBuffers b;
@@ -268,7 +255,7 @@ extern "C" int ma_smooth_flow(ma_ctx* ctx, const float* flow, int H, int W, cons
         return fs_launch<kind()>(ctx, flow, H, W, wt, r, mode, min_support, b.aux, b.ws, out, counter);
     });
     MA_TRY(wf_finish(ctx, b, rc, nullptr));
-    if (unsupported_host) MA_TRY(wf_read_counters(ctx, counter, 1, unsupported_host));
+    if (unsupported_host) MA_TRY(ma_read_call_counts(ctx, counter, 1, unsupported_host));
     return MA_OK;
 }
 
@@ -286,7 +273,7 @@ extern "C" int ma_flow_fold_mask(ma_ctx* ctx, const float* flow, int H, int W, i
     MA_HIP(hipSetDevice(ctx->device));
     // the counters are always kept on the device (the kernels add to them); read back only on request
     unsigned long long* counter;
-    MA_TRY(wf_counters(ctx, true, 3, &counter));
+    MA_TRY(ma_call_counts(ctx, true, 3, &counter));
     unsigned char* bad = (unsigned char*)ma_pool_alloc(ctx, (size_t)H * W);
     if (!bad) return MA_ENOMEM;
     hipLaunchKernelGGL(fs_bad_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const float2*)flow, H, W, nbx1, bad, counter);
@@ -294,6 +281,6 @@ extern "C" int ma_flow_fold_mask(ma_ctx* ctx, const float* flow, int H, int W, i
                        counter);
     ma_pool_free(ctx, bad);
     MA_HIP(hipGetLastError());
-    if (counts_host) MA_TRY(wf_read_counters(ctx, counter, 3, counts_host));
+    if (counts_host) MA_TRY(ma_read_call_counts(ctx, counter, 3, counts_host));
     return MA_OK;
 }

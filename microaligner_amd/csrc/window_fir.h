@@ -14,9 +14,9 @@
 //   - output: lane = line, and a line of the input is a column of the output, so the stores are coalesced as well: the row
 //     pass writes its planes transposed, the column pass ends in the user's own epilogue and writes row-major.
 // What is stated here: the tile's constants, the tap table and its setup, one plane of a row pass (wf_row_plane) and the host
-// side of a call: the tap check, the shape of the launches, the counters of the ctx workspace, and the pool buffers of a call
-// with their unwinding and the read-back of per-cell counts (wf_acquire, wf_finish).  The weight that three of the users
-// take is weight_map.h.  The column kernels, and the row kernel of the flow smoothing, stage and filter in their own bodies,
+// side of a call: the tap check, the shape of the launches, and the pool buffers of a call with their unwinding and the
+// read-back of per-cell counts (wf_acquire, wf_finish).  The weight that three of the users take is weight_map.h, the
+// per-call counts of the smoothing and the refinement call_counts.h.  The column kernels, and the row kernel of the flow smoothing, stage and filter in their own bodies,
 // in the words of wf_row_plane: they were compiled as one body, and taken out into a function they compile to other code.
 // So does the per-cell class counter of tx_col_kernel and lc_col_kernel (the `while (todo)` loop with the ballots): as one
 // templated function it changed 1395 of the 12552 lines of texture.hip's device assembly and 4602 of local_correlation.hip's.
@@ -130,26 +130,6 @@ inline int wf_shape(int H, int W, int r, const char* what, const void* row, cons
         MA_HIP(hipFuncSetAttribute(row, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds));
         MA_HIP(hipFuncSetAttribute(col, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds));
     }
-    return MA_OK;
-}
-
-// the device counters of a call (n of them, zeroed) in the ctx workspace, if the caller asked for counts
-inline int wf_counters(ma_ctx* ctx, bool wanted, int n, unsigned long long** counter)
-{
-    *counter = nullptr;
-    if (!wanted) return MA_OK;
-    MA_TRY(ma_ws_reserve(ctx, n * sizeof(unsigned long long)));
-    MA_TRY(ma_pinned_reserve(ctx, n * sizeof(unsigned long long)));
-    *counter = (unsigned long long*)ctx->ws;
-    MA_HIP(hipMemsetAsync(*counter, 0, n * sizeof(unsigned long long), ctx->stream));
-    return MA_OK;
-}
-
-inline int wf_read_counters(ma_ctx* ctx, const unsigned long long* counter, int n, long long* host)
-{
-    MA_HIP(hipMemcpyAsync(ctx->pinned, counter, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    MA_HIP(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < n; k++) host[k] = (long long)((const unsigned long long*)ctx->pinned)[k];
     return MA_OK;
 }
 

@@ -321,7 +321,7 @@ def test_the_source_hash_is_the_parents(tmp_path, monkeypatch):
     assert _lib.source_hash() == before
     assert "flow_affine.hip" in build.SOURCES and "microaligner_flowaffine.h" not in " ".join(build.HEADERS)
     own = [os.path.basename(h) for h in build.SOURCE_HEADERS["flow_affine.hip"]]
-    assert own == ["microaligner_flowaffine.h", "microaligner_flowsmooth.h", "cell_grid.h", "weight_map.h"]
+    assert own == ["microaligner_flowaffine.h", "microaligner_flowsmooth.h", "cell_grid.h", "weight_map.h", "moment_sums.h"]
     monkeypatch.setattr(build, "SOURCES", [s for s in build.SOURCES if s != "flow_affine.hip"])
     monkeypatch.setattr(build, "SOURCE_HEADERS", {k: v for k, v in build.SOURCE_HEADERS.items() if k != "flow_affine.hip"})
     assert build.source_hash() == before

@@ -171,7 +171,7 @@ def test_the_source_hash_is_the_parents(monkeypatch):
     assert before == "19a3cec2ac2dae56" and _lib.source_hash() == before
     assert "flow_fill.hip" in build.SOURCES and "microaligner_flowfill.h" not in " ".join(build.HEADERS)
     own = [os.path.basename(h) for h in build.SOURCE_HEADERS["flow_fill.hip"]]
-    assert own == ["microaligner_flowfill.h", "microaligner_flowsmooth.h", "weight_map.h"]
+    assert own == ["microaligner_flowfill.h", "microaligner_flowsmooth.h", "weight_map.h", "call_counts.h"]
     monkeypatch.setattr(build, "SOURCES", [s for s in build.SOURCES if s != "flow_fill.hip"])
     monkeypatch.setattr(build, "SOURCE_HEADERS", {k: v for k, v in build.SOURCE_HEADERS.items() if k != "flow_fill.hip"})
     assert build.source_hash() == before

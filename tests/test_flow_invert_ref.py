@@ -271,7 +271,8 @@ def test_header_library_and_bindings_agree():
 def test_flow_invert_stays_out_of_the_measured_path_hash(tmp_path, monkeypatch):
     from microaligner_amd import build
     assert "flow_invert.hip" in build.SOURCES and HEADER not in [os.path.abspath(h) for h in build.HEADERS]
-    assert [os.path.abspath(h) for h in build.SOURCE_HEADERS["flow_invert.hip"]] == [HEADER]
+    assert [os.path.abspath(h) for h in build.SOURCE_HEADERS["flow_invert.hip"]] == [HEADER,
+                                                                                     os.path.join(build.CSRC, "call_counts.h")]
     before = build.source_hash()
     csrc = tmp_path / "csrc"
     shutil.copytree(build.CSRC, csrc)

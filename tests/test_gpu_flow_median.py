@@ -329,7 +329,7 @@ def test_the_source_hash_is_the_parents(tmp_path, monkeypatch):
     assert _lib.source_hash() == before
     assert "flow_median.hip" in build.SOURCES and "microaligner_flowmedian.h" not in " ".join(build.HEADERS)
     own = [os.path.basename(h) for h in build.SOURCE_HEADERS["flow_median.hip"]]
-    assert own == ["microaligner_flowmedian.h", "microaligner_flowsmooth.h", "weight_map.h"]
+    assert own == ["microaligner_flowmedian.h", "microaligner_flowsmooth.h", "weight_map.h", "call_counts.h"]
     monkeypatch.setattr(build, "SOURCES", [s for s in build.SOURCES if s != "flow_median.hip"])
     monkeypatch.setattr(build, "SOURCE_HEADERS", {k: v for k, v in build.SOURCE_HEADERS.items() if k != "flow_median.hip"})
     assert build.source_hash() == before

@@ -315,4 +315,5 @@ def test_the_source_hash_is_the_parents():
     assert "flow_refine.hip" in build.SOURCES and "microaligner_flowrefine.h" not in " ".join(build.HEADERS)
     assert [os.path.basename(h) for h in build.SOURCE_HEADERS["flow_refine.hip"]] == ["microaligner_flowrefine.h",
                                                                                       "microaligner_flowsmooth.h",
-                                                                                      "window_fir.h", "weight_map.h"]
+                                                                                      "window_fir.h", "weight_map.h",
+                                                                                      "call_counts.h"]

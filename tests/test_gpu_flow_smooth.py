@@ -356,7 +356,8 @@ def test_the_source_hash_is_the_parents(tmp_path, monkeypatch):
     assert _lib.source_hash() == before
     assert "flow_smooth.hip" in build.SOURCES and "microaligner_flowsmooth.h" not in " ".join(build.HEADERS)
     own = [os.path.basename(h) for h in build.SOURCE_HEADERS["flow_smooth.hip"]]
-    assert own == ["microaligner_flowsmooth.h", "cell_grid.h", "flow_jacobian.h", "window_fir.h", "weight_map.h"]
+    assert own == ["microaligner_flowsmooth.h", "cell_grid.h", "flow_jacobian.h", "window_fir.h", "weight_map.h",
+                   "call_counts.h"]
     assert "flow_jacobian.h" in [os.path.basename(h) for h in build.SOURCE_HEADERS["qc.hip"]]
     monkeypatch.setattr(build, "SOURCES", [s for s in build.SOURCES if s != "flow_smooth.hip"])
     monkeypatch.setattr(build, "SOURCE_HEADERS", {k: v for k, v in build.SOURCE_HEADERS.items() if k != "flow_smooth.hip"})
