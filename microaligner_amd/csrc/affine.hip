@@ -54,37 +54,6 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const T* __restrict__ 
     dst[(size_t)r * w + c] = (T)out;  // ndarray.astype: truncation toward zero for the integer dtypes
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void mm_partial(const T* __restrict__ src, size_t n, float* __restrict__ part)
-{
-    float lo = INFINITY, hi = -INFINITY;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        float v = (float)src[i];
-        lo = fminf(lo, v); hi = fmaxf(hi, v);
-    }
-    for (int off = 32; off > 0; off >>= 1) { lo = fminf(lo, __shfl_down(lo, off)); hi = fmaxf(hi, __shfl_down(hi, off)); }
-    __shared__ float slo[4], shi[4];
-    if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[blockIdx.x * 2] = fminf(fminf(slo[0], slo[1]), fminf(slo[2], slo[3]));
-        part[blockIdx.x * 2 + 1] = fmaxf(fmaxf(shi[0], shi[1]), fmaxf(shi[2], shi[3]));
-    }
-}
-__global__ __launch_bounds__(256) void mm_final(const float* __restrict__ part, int nparts, float* __restrict__ out)
-{
-    float lo = INFINITY, hi = -INFINITY;
-    for (int i = threadIdx.x; i < nparts; i += 256) { lo = fminf(lo, part[i * 2]); hi = fmaxf(hi, part[i * 2 + 1]); }
-    for (int off = 32; off > 0; off >>= 1) { lo = fminf(lo, __shfl_down(lo, off)); hi = fmaxf(hi, __shfl_down(hi, off)); }
-    __shared__ float slo[4], shi[4];
-    if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = fminf(fminf(slo[0], slo[1]), fminf(slo[2], slo[3]));
-        out[1] = fmaxf(fmaxf(shi[0], shi[1]), fmaxf(shi[2], shi[3]));
-    }
-}
-
 } // namespace
 
 extern "C" int ma_warp_affine(ma_ctx* ctx, const void* src, int dtype, int h, int w, const double* inverse_3x3,
@@ -102,25 +71,23 @@ extern "C" int ma_warp_affine(ma_ctx* ctx, const void* src, int dtype, int h, in
     else { affine_row = a.m[6] == 0 && a.m[7] == 0 && a.m[8] == 1; noshear = a.m[1] == 0 && a.m[3] == 0; }
     a.mode = affine_row ? (noshear ? 0 : 1) : 2;
     const size_t n = (size_t)h * w;
-    const int blocks = (int)std::min<size_t>(1024, (n + 2047) / 2048);
-    MA_TRY(ma_dconst_reserve(ctx, (1024 * 2 + 8) * sizeof(float)));
+    // part sits at the start of dconst (a device allocation): 8-byte aligned, as minmax_final reads it
+    MA_TRY(ma_dconst_reserve(ctx, (MA_MINMAX_PART_FLOATS + 8) * sizeof(float)));
     float* part = (float*)ctx->dconst;
-    float* mm = part + 2048;
+    float* mm = part + MA_MINMAX_PART_FLOATS;
     MaProfScope ps(ctx, MA_K_OTHER, (double)n);
+    // The shared final fold starts from (FLT_MAX, -FLT_MAX), not from +-INFINITY.  The two differ only for a float32 image
+    // whose every value is +Inf or NaN (lo: FLT_MAX, not +Inf) or -Inf or NaN (hi: -FLT_MAX, not -Inf).  From such an
+    // image warp_affine_kernel computes nothing but +-Inf, NaN and the 0 outside the source; its clip leaves +-Inf and NaN
+    // as they are under either seed, and 0, outside both ranges, is kept by the keep0 rule.
+    MA_TRY(ma_launch_minmax(ctx, src, dtype, n, part, mm));
     dim3 grid((w + 255) / 256, h), block(256);
-    if (dtype == MA_U8) {
-        hipLaunchKernelGGL((mm_partial<uint8_t>), dim3(blocks), dim3(256), 0, ctx->stream, (const uint8_t*)src, n, part);
-        hipLaunchKernelGGL(mm_final, dim3(1), dim3(256), 0, ctx->stream, part, blocks, mm);
+    if (dtype == MA_U8)
         hipLaunchKernelGGL((warp_affine_kernel<uint8_t, double>), grid, block, 0, ctx->stream, (const uint8_t*)src, h, w, a, mm, (uint8_t*)dst);
-    } else if (dtype == MA_U16) {
-        hipLaunchKernelGGL((mm_partial<uint16_t>), dim3(blocks), dim3(256), 0, ctx->stream, (const uint16_t*)src, n, part);
-        hipLaunchKernelGGL(mm_final, dim3(1), dim3(256), 0, ctx->stream, part, blocks, mm);
+    else if (dtype == MA_U16)
         hipLaunchKernelGGL((warp_affine_kernel<uint16_t, double>), grid, block, 0, ctx->stream, (const uint16_t*)src, h, w, a, mm, (uint16_t*)dst);
-    } else {
-        hipLaunchKernelGGL((mm_partial<float>), dim3(blocks), dim3(256), 0, ctx->stream, (const float*)src, n, part);
-        hipLaunchKernelGGL(mm_final, dim3(1), dim3(256), 0, ctx->stream, part, blocks, mm);
+    else
         hipLaunchKernelGGL((warp_affine_kernel<float, float>), grid, block, 0, ctx->stream, (const float*)src, h, w, a, mm, (float*)dst);
-    }
     MA_HIP(hipGetLastError());
     return MA_OK;
 }

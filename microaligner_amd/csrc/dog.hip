@@ -15,21 +15,6 @@
 namespace {
 
 // ---- min / max ------------------------------------------------------------------------------
-__device__ __forceinline__ void block_minmax_256(float lo, float hi, float* out2)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_down(lo, off));
-        hi = fmaxf(hi, __shfl_down(hi, off));
-    }
-    __shared__ float slo[4], shi[4];
-    if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out2[0] = fminf(fminf(slo[0], slo[1]), fminf(slo[2], slo[3]));
-        out2[1] = fmaxf(fmaxf(shi[0], shi[1]), fmaxf(shi[2], shi[3]));
-    }
-}
-
 // 16 bytes per lane and load; head/tail elements that do not fill an aligned 16-byte group go one by one
 template <typename T>
 __global__ __launch_bounds__(256) void minmax_partial(const T* __restrict__ src, size_t n, float* __restrict__ part)
@@ -64,7 +49,8 @@ __global__ __launch_bounds__(256) void minmax_partial(const T* __restrict__ src,
     }
     for (size_t i = tid; i < head; i += stride) { float f = (float)src[i]; lo = fminf(lo, f); hi = fmaxf(hi, f); }
     for (size_t i = head + nvec * E + tid; i < n; i += stride) { float f = (float)src[i]; lo = fminf(lo, f); hi = fmaxf(hi, f); }
-    block_minmax_256(lo, hi, part + blockIdx.x * 2);
+    __shared__ float s_lo[4], s_hi[4];
+    d_block_minmax_in<4>(lo, hi, s_lo, s_hi, [&](float l, float h) { part[blockIdx.x * 2] = l; part[blockIdx.x * 2 + 1] = h; });
 }
 
 // scalars of the DOG chain, produced and consumed on the device
@@ -141,22 +127,16 @@ __global__ __launch_bounds__(MMF_T) void minmax_final(const float* __restrict__ 
 #pragma unroll
         for (int u = 0; u < 4; u++) { lo = fminf(lo, v[u].x); hi = fmaxf(hi, v[u].y); }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_down(lo, off));
-        hi = fmaxf(hi, __shfl_down(hi, off));
-    }
-    __shared__ float slo[MMF_T / 64], shi[MMF_T / 64];
-    if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < MMF_T / 64; k++) { lo = fminf(lo, slo[k]); hi = fmaxf(hi, shi[k]); }
-        if (out) { out[0] = lo; out[1] = hi; }
-        if (what == 1) d_dog_params_in(sc, lo, hi);
-        else if (what == 2) d_dog_params_out(sc, lo, hi, sticky);
-    }
+    __shared__ float s_lo[MMF_T / 64], s_hi[MMF_T / 64];
+    d_block_minmax_in<MMF_T / 64>(lo, hi, s_lo, s_hi, [&](float l, float h) {
+        if (out) { out[0] = l; out[1] = h; }
+        if (what == 1) d_dog_params_in(sc, l, h);
+        else if (what == 2) d_dog_params_out(sc, l, h, sticky);
+    });
 }
 
 constexpr int MM_BLOCKS = 2048;
+static_assert(MA_MINMAX_PART_FLOATS == 2 * MM_BLOCKS, "one (min, max) pair per block of minmax_partial");
 
 int launch_minmax(ma_ctx* ctx, const void* src, int dtype, size_t n, float* part, float* out2, DogScalars* sc = nullptr,
                   int what = 0)
@@ -286,10 +266,8 @@ __global__ __launch_bounds__(64 * NW) void dog_cols_diff(const float* __restrict
             lo = fminf(lo, d); hi = fmaxf(hi, d);
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_down(lo, off));
-        hi = fmaxf(hi, __shfl_down(hi, off));
-    }
+    // the fold of d_block_minmax_in, by hand on the scalar wave index (see there)
+    d_wave_minmax(lo, hi);
     __shared__ float slo[NW], shi[NW];
     if (lane == 0) { slo[wv] = lo; shi[wv] = hi; }
     __syncthreads();
@@ -457,10 +435,8 @@ __global__ __launch_bounds__(64 * DF_NW, 2) void dog_fused(const T* __restrict__
         }
     }
     // block min / max through the (now idle) dynamic LDS: no static allocation, the block's budget is exactly 2 per CU
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_down(lo, off));
-        hi = fmaxf(hi, __shfl_down(hi, off));
-    }
+    // (the fold of d_block_minmax_in, by hand on the scalar wave index: see there)
+    d_wave_minmax(lo, hi);
     __syncthreads();
     if (lane == 0) { lds[wv] = lo; lds[DF_NW + wv] = hi; }
     __syncthreads();
@@ -591,6 +567,11 @@ DogPlan dog_plan(int h, int w, int low_sigma)
 } // namespace
 
 size_t ma_dog_workspace_bytes(int h, int w, int low_sigma) { return dog_plan(h, w, low_sigma).bytes; }
+
+int ma_launch_minmax(ma_ctx* ctx, const void* src, int dtype, size_t n, float* part, float* out2)
+{
+    return launch_minmax(ctx, src, dtype, n, part, out2);
+}
 
 int ma_launch_minmax_final(ma_ctx* ctx, const float* part, int nparts, float* out2)
 {

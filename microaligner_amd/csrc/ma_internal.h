@@ -426,23 +426,46 @@ __device__ __forceinline__ void d_sym_fir_ring_pk(const float* __restrict__ col,
     for (int r = 0; r < H; r++) { acc[r] = A[r].x; acc[r + H] = A[r].y; }
 }
 
-// Block-wide (min, max) of per-thread values -> part[0], part[1] (thread 0 writes).  All threads of the block must
-// call it; blocks of up to 1024 threads.
-__device__ __forceinline__ void d_block_minmax(float lo, float hi, float* part)
+// The float (min, max) reduction, stated once.  No operand is NaN (the seeds are +-INFINITY or +-FLT_MAX, fminf / fmaxf
+// drop a NaN operand), so the result does not depend on the order of the fold.
+// Wave: the shuffle tree; lane 0 holds the wave's (min, max).
+__device__ __forceinline__ void d_wave_minmax(float& lo, float& hi)
 {
     for (int off = 32; off > 0; off >>= 1) {
         lo = fminf(lo, __shfl_down(lo, off));
         hi = fmaxf(hi, __shfl_down(hi, off));
     }
-    __shared__ float s_lo[16], s_hi[16];
-    const int nw = (blockDim.x * blockDim.y * blockDim.z + 63) >> 6;
+}
+// Block of NW waves (NW = 0: the wave count of the launch), LDS from the caller: s_lo and s_hi hold one float per wave each
+// that nothing else uses from this call on.  Lane 0 of each wave stores to them, one barrier, thread 0 folds waves
+// 1 .. NW - 1 in sequence and hands the block's (min, max) to out(lo, hi), which writes them where the caller wants them.
+// All threads of the block must call it.  (A callable and not a returned flag: with a flag the compiler splits thread 0's
+// branch in two, and pyr_down_kernel and warp_tiled_kernel would no longer compile to what they were.)
+// dog_cols_diff and dog_fused (dog.hip) state this fold by hand over d_wave_minmax: it reads their scalar wave index, and
+// with the helper's own the compiler allocates the registers of the whole kernel differently.
+template <int NW, typename Out>
+__device__ __forceinline__ void d_block_minmax_in(float lo, float hi, float* s_lo, float* s_hi, Out out)
+{
+    d_wave_minmax(lo, hi);
+    const int nw = NW ? NW : (blockDim.x * blockDim.y * blockDim.z + 63) >> 6;
     if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int k = 1; k < nw; k++) { lo = fminf(lo, s_lo[k]); hi = fmaxf(hi, s_hi[k]); }
-        part[0] = lo; part[1] = hi;
+        out(lo, hi);
     }
 }
+// Block-wide (min, max) of per-thread values -> part[0], part[1] (thread 0 writes), LDS of its own; blocks of up to 1024
+// threads.
+__device__ __forceinline__ void d_block_minmax(float lo, float hi, float* part)
+{
+    __shared__ float s_lo[16], s_hi[16];
+    d_block_minmax_in<0>(lo, hi, s_lo, s_hi, [&](float l, float h) { part[0] = l; part[1] = h; });
+}
+// (min, max) of n elements of a device array -> out2[0..1], on the device and stream ordered (dog.hip): partials of 16-byte
+// loads into part (MA_MINMAX_PART_FLOATS floats, 8-byte aligned), folded from (FLT_MAX, -FLT_MAX)
+constexpr int MA_MINMAX_PART_FLOATS = 2 * 2048;
+int ma_launch_minmax(ma_ctx* ctx, const void* src, int dtype, size_t n, float* part, float* out2);
 // folds nparts (min, max) pairs on the device into out2[0..1] (dog.hip); stream ordered
 int ma_launch_minmax_final(ma_ctx* ctx, const float* part, int nparts, float* out2);
 

@@ -153,6 +153,14 @@ __device__ __forceinline__ float key2f(unsigned k)
 }
 // NaN-propagating maximum (fmaxf drops NaNs)
 __device__ __forceinline__ float d_max_nan(float m, float v) { return (m != m || v != v) ? NAN : fmaxf(m, v); }
+// wave-wide d_max_nan of two values at once; lane 0 holds the results
+__device__ __forceinline__ void d_wave_max_nan2(float& m1, float& m2)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        m1 = d_max_nan(m1, __shfl_down(m1, off));
+        m2 = d_max_nan(m2, __shfl_down(m2, off));
+    }
+}
 // Segment of coordinate v along an axis cut at the window borders k*T - ov and k*T + ov (T > 2*ov):
 // zone_k = [k*T - ov, k*T + ov) has index 2k, core_k = [k*T + ov, (k+1)*T - ov) index 2k+1; window t is the union of
 // segments 2t, 2t+1, 2t+2 (see cell_max_kernel).
@@ -291,10 +299,7 @@ __global__ __launch_bounds__(256) void window_max_kernel(const float2* __restric
             m1 = d_max_nan(m1, d_max_nan(a.x, a.y));
             m2 = d_max_nan(m2, d_max_nan(b.x, b.y));
         }
-    for (int off = 32; off > 0; off >>= 1) {
-        m1 = d_max_nan(m1, __shfl_down(m1, off));
-        m2 = d_max_nan(m2, __shfl_down(m2, off));
-    }
+    d_wave_max_nan2(m1, m2);
     if ((threadIdx.x & 63) == 0) {
         atomicMax(&maxkeys[widx * 2], f2key(m1));
         atomicMax(&maxkeys[widx * 2 + 1], f2key(m2));
@@ -334,10 +339,7 @@ __global__ __launch_bounds__(256) void cell_max_kernel(const float2* __restrict_
             m1 = d_max_nan(m1, d_max_nan(a.x, a.y));
             m2 = d_max_nan(m2, d_max_nan(b.x, b.y));
         }
-    for (int off = 32; off > 0; off >>= 1) {
-        m1 = d_max_nan(m1, __shfl_down(m1, off));
-        m2 = d_max_nan(m2, __shfl_down(m2, off));
-    }
+    d_wave_max_nan2(m1, m2);
     if ((threadIdx.x & 63) == 0) {
         unsigned* c = cellkeys + ((size_t)segy * nsegx + blockIdx.x) * 2;
         atomicMax(&c[0], f2key(m1));

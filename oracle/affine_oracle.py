@@ -29,7 +29,8 @@ def inverse_matrix(tmat):
     return np.linalg.pinv(np.append(np.asarray(tmat, dtype=np.float64), [[0, 0, 1]], axis=0))
 
 
-def warp_with_inverse(img, inv):
+def warp_with_inverse(img, inv, bounds=None):
+    """bounds: the (lo, hi) that the output is clipped to; None: the image's min() and max(), as skimage takes them"""
     ft = np.float32 if img.dtype == np.float32 else np.float64
     H, W = img.shape
     im = img.astype(ft)
@@ -61,7 +62,7 @@ def warp_with_inverse(img, inv):
     top = (one - dc) * px(minr, minc) + dc * px(minr, maxc)
     bot = (one - dc) * px(maxr, minc) + dc * px(maxr, maxc)
     out = ((one - dr) * top + dr * bot).astype(ft)
-    lo, hi = im.min(), im.max()
+    lo, hi = (im.min(), im.max()) if bounds is None else (ft(bounds[0]), ft(bounds[1]))
     keep = (out == 0) if not (lo <= 0 <= hi) else None
     out = np.clip(out, lo, hi)
     if keep is not None:

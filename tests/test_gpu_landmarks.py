@@ -307,5 +307,5 @@ def test_c_entries_refuse_bad_arguments_without_launching(ctx):
 
 def test_the_loaded_library_is_this_trees():
     from microaligner_amd import build
-    assert _lib.source_hash() == build.source_hash() == "19a3cec2ac2dae56"
+    assert _lib.source_hash() == build.source_hash() == "c8c3e3bfcfe3f943"
     assert hasattr(_lib.load(), "ma_landmark_flow") and hasattr(_lib.load(), "ma_landmark_points")

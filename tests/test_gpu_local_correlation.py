@@ -304,4 +304,4 @@ def test_the_library_exports_the_entry_and_carries_the_parents_hash():
     from microaligner_amd import build
     lib = _lib.load()
     assert hasattr(lib, "ma_local_correlation"), "ma_local_correlation declared in microaligner_localcorr.h but not exported"
-    assert build.source_hash() == "19a3cec2ac2dae56" == _lib.source_hash()
+    assert build.source_hash() == "c8c3e3bfcfe3f943" == _lib.source_hash()

@@ -347,6 +347,36 @@ def test_dog_special_cases_and_minmax(ctx):
     assert np.array_equal(reg.dog(img, True), O.dog(img, True))
 
 
+# n below, at and above one 16-byte group of the partial reduction for f32 (4 elements) and u8 (16), and more than one block
+# of 256 x 8 elements plus a tail.  (No other test gives ctx.minmax a 1 x n image of one of these sizes: this file has 99 x 77,
+# test_nonfinite.py whole images of thousands of pixels; and warp_affine used to have a reduction of its own.)
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 15, 16, 17, 256 * 8 * 2 + 3])
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.float32])
+def test_minmax_and_warp_affine_at_the_edges_of_the_partial_reduction(ctx, dtype, n):
+    """The extreme value stands in turn at element 0, at the last element and at the first element behind the last full
+    16-byte group.  warp_affine shows the minimum it was given: half a pixel along x blends the last pixel with the 0
+    outside to half its value, below every grey level of the image, and the clip raises it to the minimum (0 is outside
+    the range); for the negated float image it shows the maximum in the same way."""
+    from oracle import affine_oracle as A
+    per_group = 16 // np.dtype(dtype).itemsize
+    inv = np.array([[1.0, 0.0, 0.5], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])
+    base = np.random.default_rng(n).integers(100, 119, (1, n)).astype(dtype)
+    top = np.iinfo(dtype).max if dtype != np.float32 else np.float32(3e38)
+    variants = [(base, 60), (base, top)]
+    if dtype == np.float32:
+        variants += [(-base, -60), (-base, -top)]
+    for b, extreme in variants:
+        for pos in sorted({0, n - 1, min(n // per_group * per_group, n - 1)}):
+            img = b.copy()
+            img[0, pos] = extreme
+            d = ctx.asdevice(img)
+            assert ctx.minmax(d) == O.minmax(img), (extreme, pos)
+            exp = A.warp_with_inverse(img, inv).astype(dtype)
+            assert np.array_equal(ctx.warp_affine(d, inv).numpy(), exp), (extreme, pos)
+            if abs(float(extreme)) == 60:
+                assert exp[0, -1] == extreme      # the clip range is seen
+
+
 def test_max_project_and_normalize_u8(ctx):
     rng = np.random.default_rng(0)
     stack = rng.integers(0, 60000, (5, 120, 130)).astype(np.uint16)
