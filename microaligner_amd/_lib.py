@@ -291,6 +291,14 @@ FLOWFILL_SIGNATURES = {
     "ma_fill_flow": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_localnorm.h (local contrast normalisation of an
+# image); the weight kinds are those of microaligner_flowsmooth.h
+MA_LOCALNORM_MAX_RADIUS, MA_LOCALNORM_COUNTS = 128, 4
+LOCALNORM_SIGNATURES = {
+    "ma_normalize_local": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_f), _i, _f, _f, _vp, _i, _f, _vp, _vp,
+                                C.POINTER(C.c_longlong)]),
+}
+
 # name -> (restype, argtypes): exactly the symbols of include/microaligner_debug.h (test hook: fill idle scratch memory)
 DEBUG_SIGNATURES = {
     "ma_debug_fill_idle": (_i, [_vp, _i, C.POINTER(C.c_ulonglong)]),
@@ -316,7 +324,7 @@ def load():
             list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()) + \
             list(LANDMARK_SIGNATURES.items()) + list(TRANSLATION_SIGNATURES.items()) + \
             list(QUANTILE_SIGNATURES.items()) + list(LOCALCORR_SIGNATURES.items()) + list(FLOWMEDIAN_SIGNATURES.items()) + \
-            list(FLOWFILL_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
+            list(FLOWFILL_SIGNATURES.items()) + list(LOCALNORM_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -16,7 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
            "flow_compose.hip", "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip", "texture.hip", "direct_affine.hip", "flow_refine.hip",
-           "landmarks.hip", "translation.hip", "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip", "debug_fill.hip"]
+           "landmarks.hip", "translation.hip", "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip", "debug_fill.hip",
+           "local_norm.hip"]
 
 
 def _inc(name):
@@ -32,9 +33,10 @@ _INTERP_HEADERS = [_inc("microaligner_interp.h"), os.path.join(CSRC, "remap_inte
 _CELL_GRID = os.path.join(CSRC, "cell_grid.h")
 _FLOW_GRID = [_inc("microaligner_flowgrid.h"), os.path.join(CSRC, "flow_grid_eval.h")]
 _FLOW_JACOBIAN = os.path.join(CSRC, "flow_jacobian.h")   # det J, stated once for the quality maps and the fold mask
-# the separable FIR tile of the smoothing, the texture maps, the refinement and the local correlation maps
+# the separable FIR tile of the smoothing, the texture maps, the refinement, the local correlation maps and the local
+# contrast normalisation
 _WINDOW_FIR = os.path.join(CSRC, "window_fir.h")
-# the weight argument of the seven calls that take one: its readers on the device, its check and dispatch at the C entry
+# the weight argument of the eight calls that take one: its readers on the device, its check and dispatch at the C entry
 _WEIGHT_MAP = os.path.join(CSRC, "weight_map.h")
 # the per-call event counts: the wave tally of the kernels, the counters of the ctx workspace and their read-back
 _CALL_COUNTS = os.path.join(CSRC, "call_counts.h")
@@ -58,7 +60,8 @@ SOURCE_HEADERS = {"qc.hip": [_inc("microaligner_qc.h"), _CELL_GRID, _FLOW_JACOBI
                   "local_correlation.hip": [_inc("microaligner_localcorr.h"), _SMOOTH_H, _CELL_GRID, _WINDOW_FIR, _WEIGHT_MAP],
                   "flow_median.hip": [_inc("microaligner_flowmedian.h"), _SMOOTH_H, _WEIGHT_MAP, _CALL_COUNTS],
                   "flow_fill.hip": [_inc("microaligner_flowfill.h"), _SMOOTH_H, _WEIGHT_MAP, _CALL_COUNTS],
-                  "debug_fill.hip": [_inc("microaligner_debug.h")]}
+                  "debug_fill.hip": [_inc("microaligner_debug.h")],
+                  "local_norm.hip": [_inc("microaligner_localnorm.h"), _SMOOTH_H, _WINDOW_FIR, _WEIGHT_MAP, _CALL_COUNTS]}
 # the grid-flow headers are also read by the two sources whose kernels take their flow from a grid: further dependencies of
 # those sources, beside the headers of their own above
 GRID_FLOW_USERS = {"warp_compose.hip": _FLOW_GRID, "flow_invert.hip": _FLOW_GRID}
@@ -123,17 +126,20 @@ def source_hash():
     #   - the local correlation maps (windowed ZNCC of a registered pair), which only local_correlation() reaches;
     #   - the median filter of a flow and its outlier mask, which only median_flow() / outlier_mask() reach;
     #   - the push-pull fill of a flow (a weighted pyramid pulled to 1 x 1 and pushed back), which only fill_flow() reaches;
+    #   - the local contrast normalisation (an image minus its windowed mean over its windowed standard deviation), which
+    #     only normalize_local() reaches;
     #   - the test hook that fills a context's idle scratch memory, which only tests call and which launches no kernel;
     #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps, flow_jacobian.h, det J of
     #     the quality maps and the fold mask, window_fir.h, the separable FIR tile of the flow smoothing, the texture
-    #     maps, the flow refinement and the local correlation maps, weight_map.h, the weight argument of the seven
-    #     calls above that take one, call_counts.h, the per-call event counts of the flow calls above that return some,
+    #     maps, the flow refinement, the local correlation maps and the local contrast normalisation, weight_map.h, the
+    #     weight argument of the eight calls above that take one, call_counts.h, the per-call event counts of the calls above that return some,
     #     and moment_sums.h, the fixed-order float64 reduction of the two kinds of affine moments (SOURCE_HEADERS).
     off_path = {"probe.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "affine.hip", "qc.hip",
                 "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip", "flow_compose.hip",
                 "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip",
                 "texture.hip", "direct_affine.hip", "flow_refine.hip", "landmarks.hip", "translation.hip",
-                "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip", "debug_fill.hip"}
+                "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip", "debug_fill.hip",
+                "local_norm.hip"}
     for path in [os.path.join(CSRC, s) for s in SOURCES if s not in off_path] + HEADERS:
         h.update(open(path, "rb").read())
     h.update(" ".join(_flags()).encode())

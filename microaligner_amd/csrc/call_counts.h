@@ -1,6 +1,7 @@
 // The event counts that a call returns beside its result (unsupported, dropped, not_converged, folded, ...), stated once:
 // how the threads of a kernel tally them and how a C entry keeps them in the ctx workspace and reads them back
-// (flow_smooth.hip, flow_median.hip, flow_fill.hip, flow_invert.hip; flow_refine.hip for the host side).  Off the measured
+// (flow_smooth.hip, flow_median.hip, flow_fill.hip, flow_invert.hip; flow_refine.hip for the host side, local_norm.hip for
+// the wave tally: its four counters are those of window_fir.h's wf_acquire).  Off the measured
 // path: nothing in register() or warp() reaches it (a header of single sources, build.SOURCE_HEADERS).
 //
 // Integer adds only, so the totals do not depend on the order in which the waves arrive: two calls give the same counts.

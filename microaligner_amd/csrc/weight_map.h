@@ -1,5 +1,5 @@
 // The weight argument of the calls that take one (flow_smooth.hip, flow_median.hip, flow_fill.hip, flow_affine.hip,
-// direct_affine.hip, flow_refine.hip, local_correlation.hip), stated once: how a kernel reads weight(p) of include/microaligner_flowsmooth.h and
+// direct_affine.hip, flow_refine.hip, local_correlation.hip, local_norm.hip), stated once: how a kernel reads weight(p) of include/microaligner_flowsmooth.h and
 // how a C entry checks and passes it.  Off the measured path (a header of single sources, build.SOURCE_HEADERS).
 #pragma once
 #include "../../include/microaligner_flowsmooth.h"

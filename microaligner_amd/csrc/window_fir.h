@@ -1,5 +1,5 @@
-// The separable window FIR behind the flow smoothing, the texture maps, the flow refinement and the local correlation maps
-// (flow_smooth.hip, texture.hip, flow_refine.hip, local_correlation.hip): its tile, stated once.  Off the measured path: nothing in register() or warp() reaches it (a header of
+// The separable window FIR behind the flow smoothing, the texture maps, the flow refinement, the local correlation maps and
+// the local contrast normalisation (flow_smooth.hip, texture.hip, flow_refine.hip, local_correlation.hip, local_norm.hip): its tile, stated once.  Off the measured path: nothing in register() or warp() reaches it (a header of
 // single sources, build.SOURCE_HEADERS).
 //
 // A symmetric FIR with up to 2 * WF_MAX_RADIUS + 1 taps over P planes, in two launches through a workspace of 4 P B/px that

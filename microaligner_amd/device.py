@@ -460,6 +460,44 @@ def local_correlation_params(ref, img, taps, floor, center=(0.0, 0.0), weight=No
     return H, W, rdt, taps, r, (ca, cb), floor, kind, ms, lo, hi, ch, cw, want
 
 
+# ---- local contrast normalisation of an image (include/microaligner_localnorm.h) -------------------------------------------
+LOCALNORM_PLANES = ("u8", "f32")
+
+
+class LocalNormInfo(collections.namedtuple("LocalNormInfo", "dropped unsupported flat clipped")):
+    """normalize_local(..., return_info=True): whole-image counts.  dropped: pixels that are not finite or whose weight is
+    not finite and positive; unsupported: live pixels whose window's weight is not above min_support, or whose z is NaN
+    (both kinds come out as "no contrast": 0.0 / 128); flat: supported pixels whose local variance is <= floor; clipped:
+    supported pixels with |z| > clip."""
+
+
+def local_norm_params(img, taps, floor, clip=4.0, weight=None, min_support=0.0, want=("u8",)):
+    """Checks and host-side arguments of the local contrast normalisation (include/microaligner_localnorm.h) without
+    touching a device: (H, W, dtype code, taps as C-contiguous float32, r, floor, clip, weight kind, min_support -- the
+    three scalars as float32 --, want as a tuple).  img: an (H, W) uint8, uint16 or float32 array (numpy or device); weight:
+    None, or an (H, W) float32 map or uint8 mask; want: which of "u8" and "f32" to make, at least one; clip may be +Inf
+    only without "u8".  ValueError for anything the C entry would refuse."""
+    dtype = _check_image(img, "img")
+    H, W = (int(v) for v in img.shape)
+    _image_sides(H, W)
+    taps, r = _check_taps(taps)
+    floor = _positive_f32(floor, "floor")
+    with np.errstate(over="ignore"):
+        c = float(np.float32(_real(clip, "clip")))
+    if not c > 0:
+        raise ValueError(f"clip must be > 0 as float32 and not NaN, got {clip!r}")
+    ms = _finite_f32(min_support, "min_support")
+    if not ms >= 0:
+        raise ValueError(f"min_support must not be negative, got {min_support!r}")
+    kind = _weight_kind(weight, H, W)[0]
+    if not isinstance(want, (tuple, list)) or not all(isinstance(n, str) and n in LOCALNORM_PLANES for n in want) or \
+            len(set(want)) != len(want) or not want:
+        raise ValueError(f"want must name one or both of {LOCALNORM_PLANES}, got {want!r}")
+    if "u8" in want and np.isinf(c):
+        raise ValueError("an infinite clip has no uint8 output: ask for \"f32\" alone")
+    return H, W, dtype, taps, r, floor, c, kind, ms, tuple(want)
+
+
 # ---- global translation search (include/microaligner_translation.h) --------------------------------------------------------
 def translation_params(ref, mov, window, exclude=0):
     """Checks and host-side arguments of the translation search (include/microaligner_translation.h) without touching a
@@ -1653,6 +1691,22 @@ class Context:
         if counts is not None:
             out["counts"] = counts
         return out
+
+    def normalize_local(self, img, taps, floor, clip=4.0, weight=None, min_support=0.0, want=("u8",), return_info=False):
+        """The local contrast normalisation of an (H, W) uint8, uint16 or float32 device image with the symmetric kernel
+        taps t[0 .. r] (include/microaligner_localnorm.h): z = (x - mu) / sqrt(v + floor) with the windowed mean mu and the
+        windowed variance v about it, `floor` in squared grey levels; "f32": z clipped to +-clip, "u8": z * 127 / clip + 128
+        rounded into 0 .. 255.  Pixels that are dropped (not finite, or no weight) or whose window's weight is not above
+        min_support give 0.0 / 128.  weight: None, an (H, W) float32 map or uint8 mask.  -> a dict of the planes named in
+        `want` ((H, W) device arrays); with return_info (that dict, LocalNormInfo(dropped, unsupported, flat, clipped)),
+        at the cost of a synchronisation."""
+        H, W, dtype, taps, r, floor, clip, kind, ms, want = local_norm_params(img, taps, floor, clip, weight, min_support, want)
+        out = {n: self.empty((H, W), np.uint8 if n == "u8" else np.float32) for n in want}
+        ptr = {n: (out[n].ptr if n in out else None) for n in LOCALNORM_PLANES}
+        counts = (C.c_longlong * L.MA_LOCALNORM_COUNTS)()
+        self._run(self.lib.ma_normalize_local, img.ptr, dtype, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r, floor, clip,
+                  None if weight is None else weight.ptr, kind, ms, ptr["f32"], ptr["u8"], counts if return_info else None)
+        return (out, LocalNormInfo(*(int(v) for v in counts))) if return_info else out
 
     def flow_refine_step(self, ref, warped, flow, taps, floor, weight=None, max_step=1.0, return_info=False, out=None):
         """One regularised Lucas-Kanade step of `flow` (include/microaligner_flowrefine.h): the 2 x 2 system of the

@@ -10,6 +10,8 @@ import math
 
 import numpy as np
 
+from ..device import LocalNormInfo  # noqa: F401  (what normalize_local(..., return_info=True) returns)
+
 
 class NormalizeInfo(collections.namedtuple("NormalizeInfo", "lo hi pop nonfinite zeros degenerate")):
     """normalize_percentile(..., return_info=True): the two values the image was scaled between (NaN when the population is
@@ -61,3 +63,51 @@ def normalize_percentile(img, low=0.0, high=99.9, ignore_zeros=False, on_device=
     if return_info:
         return out, NormalizeInfo(lo, hi, counts.pop, counts.nonfinite, counts.zeros, bool(degenerate))
     return out
+
+
+# ---- local contrast normalisation (include/microaligner_localnorm.h) --------------------------------------------------------
+# A gain and an offset that vary slowly over the image -- bleaching between the cycles, uneven stripping, the illumination
+# of mosaic tiles -- are what neither normalisation above removes: both fix one gain for the whole image.  Here every pixel
+# is taken relative to the Gaussian-windowed mean and standard deviation around it, so two images of one structure come out
+# with one grey level, which is what Farneback assumes of its inputs:
+#
+#     oreg.ref_img, oreg.mov_img = normalize_local(ref, floor=f), normalize_local(mov, floor=f)
+LOCALNORM_DTYPES = {"uint8": "u8", "float32": "f32"}
+
+
+def local_norm_call_params(sigma, truncate, dtype, on_device, return_info):
+    """Checks of normalize_local that are its own, without touching a device: (taps, the plane's name).  The image, floor,
+    clip, weight and min_support are device.local_norm_params'."""
+    from ..device import gaussian_taps
+    taps = gaussian_taps(sigma, truncate)
+    if isinstance(dtype, type) or isinstance(dtype, np.dtype):
+        dtype = np.dtype(dtype).name
+    if not isinstance(dtype, str) or dtype not in LOCALNORM_DTYPES:
+        raise ValueError(f'dtype must be "uint8" or "float32", got {dtype!r}')
+    for v, name in ((on_device, "on_device"), (return_info, "return_info")):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, got {v!r}")
+    return taps, LOCALNORM_DTYPES[dtype]
+
+
+def normalize_local(img, sigma=16.0, *, floor, clip=4.0, weight=None, truncate=3.0, min_support=0.0, dtype="uint8",
+                    on_device=False, return_info=False):
+    """img (uint8 / uint16 / float32, numpy or DeviceArray) with its local mean taken out and divided by its local standard
+    deviation: z = (x - mu) / sqrt(v + floor), mu and v the mean and the variance under a Gaussian window of `sigma` px cut
+    at truncate * sigma (at most 128 px).  dtype "uint8": z * 127 / clip + 128 rounded into 0 .. 255, what register() takes;
+    "float32": z clipped to +-clip (clip may be inf).  floor, in squared grey levels of img, is the variance below which a
+    window counts as empty (bare glass: its noise variance); there z goes to 0 instead of amplifying the noise.  weight:
+    None, or an (H, W) float32 map or uint8 mask (numpy or DeviceArray); pixels without weight, NaN / Inf pixels and pixels
+    whose window holds no more than min_support of weight give 0.0 / 128 and put no edge at the mask's rim.  Choose sigma
+    above the size of the structures and below the scale of the gain field.  numpy in, numpy out; a DeviceArray comes back
+    with on_device=True.  With return_info: (image, LocalNormInfo(dropped, unsupported, flat, clipped))."""
+    from ..device import DeviceArray, get_context, local_norm_params
+    taps, plane = local_norm_call_params(sigma, truncate, dtype, on_device, return_info)
+    local_norm_params(img, taps, floor, clip, weight, min_support, (plane,))        # refusals before a context is made
+    ctx = get_context()
+    dev = img if isinstance(img, DeviceArray) else ctx.asdevice(np.ascontiguousarray(img))
+    wdev = weight if weight is None or isinstance(weight, DeviceArray) else ctx.asdevice(np.ascontiguousarray(weight))
+    res = ctx.normalize_local(dev, taps, floor, clip, wdev, min_support, (plane,), return_info=bool(return_info))
+    out, info = res if return_info else (res, None)
+    out = out[plane] if on_device else out[plane].numpy()
+    return (out, info) if return_info else out
