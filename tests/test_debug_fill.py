@@ -1,8 +1,8 @@
 """The test hook that fills a context's idle scratch memory (include/microaligner_debug.h, csrc/debug_fill.hip) and the
-registry of tests/test_gpu_stale_memory.py that uses it.  CPU: the header <-> library <-> bindings agreement, the measured
-path's source hash, refused arguments that need no device, and the completeness of the registry -- every C entry of the
-bindings is either exercised by a case on stale scratch memory or named in EXEMPT, which may only hold entries that launch
-no kernel over scratch memory."""
+registry of GPU cases (tests/_gpu_cases) that tests/test_gpu_stale_memory.py runs with it.  CPU: the header <-> library <->
+bindings agreement, the measured path's source hash, refused arguments that need no device, and the completeness of the
+registry -- every C entry of the bindings is either exercised by a case on stale scratch memory or named in EXEMPT, which
+may only hold entries that launch no kernel over scratch memory."""
 import ctypes as C
 import os
 import re
@@ -13,6 +13,10 @@ import sys
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+pytest.register_assert_rewrite("_gpu_cases")
+import _gpu_cases as S  # noqa: E402  (the registry: CASES, EXEMPT, declared_entries)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "microaligner_debug.h")
 
@@ -100,7 +104,6 @@ def all_entries():
 
 
 def test_every_entry_is_exercised_on_stale_memory_or_exempt():
-    import test_gpu_stale_memory as S
     entries = all_entries()
     declared = S.declared_entries()
     assert not declared - set(entries), f"cases declare entries the bindings do not have: {sorted(declared - set(entries))}"
@@ -113,7 +116,6 @@ def test_every_entry_is_exercised_on_stale_memory_or_exempt():
 
 
 def test_exempt_holds_no_compute_entry():
-    import test_gpu_stale_memory as S
     entries = all_entries()
     for name, reason in S.EXEMPT.items():
         assert isinstance(reason, str) and reason.strip(), name
@@ -127,7 +129,6 @@ def test_exempt_holds_no_compute_entry():
 
 
 def test_cases_are_named_once_and_declare_entries():
-    import test_gpu_stale_memory as S
     names = [c.name for c in S.CASES]
     assert len(names) == len(set(names)) and len(names) > 80
     for c in S.CASES:

@@ -12,6 +12,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _flow_fill_ref as R  # noqa: E402
 import _flow_smooth_ref as S  # noqa: E402
+from _measured_path import HASH  # noqa: E402
 from microaligner_amd import _lib  # noqa: E402
 from microaligner_amd.device import FillInfo, fill_flow_params  # noqa: E402
 
@@ -168,7 +169,7 @@ def test_the_source_hash_is_the_parents(monkeypatch):
     """build.source_hash() reads the files and flags it read before this source existed"""
     from microaligner_amd import build
     before = build.source_hash()
-    assert before == "c8c3e3bfcfe3f943" and _lib.source_hash() == before
+    assert before == HASH and _lib.source_hash() == before
     assert "flow_fill.hip" in build.SOURCES and "microaligner_flowfill.h" not in " ".join(build.HEADERS)
     own = [os.path.basename(h) for h in build.SOURCE_HEADERS["flow_fill.hip"]]
     assert own == ["microaligner_flowfill.h", "microaligner_flowsmooth.h", "weight_map.h", "call_counts.h"]

@@ -13,6 +13,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _flow_grid_ref as G  # noqa: E402
 import _flow_invert_ref as R  # noqa: E402
+from _measured_path import HASH  # noqa: E402
 from microaligner_amd import FlowGrid, _lib, build  # noqa: E402
 from microaligner_amd.device import affine_flow_params, affine_grid_params, grid_nodes, transform_points_params  # noqa: E402
 from microaligner_amd.optflow_reg import flow_grid as FG  # noqa: E402
@@ -311,7 +312,7 @@ def test_header_bindings_and_build_recipe_agree():
 
 def test_the_measured_path_is_untouched():
     """build.source_hash() is the value of the commit before grid flows (README, "Grid flows")"""
-    assert build.source_hash() == "c8c3e3bfcfe3f943"
+    assert build.source_hash() == HASH
 
 
 def test_entries_refuse_bad_arguments_without_a_device():

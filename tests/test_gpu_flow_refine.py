@@ -11,6 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _flow_refine_ref as R  # noqa: E402
+from _measured_path import HASH  # noqa: E402
 from _remap_interp_ref import InterpRef  # noqa: E402
 from microaligner_amd import FlowGrid, FlowRefineInfo, _lib, refine_flow  # noqa: E402
 from microaligner_amd.device import DeviceArray, RefineStepInfo, grid_nodes  # noqa: E402
@@ -311,7 +312,7 @@ def test_header_library_and_bindings_agree():
 
 def test_the_source_hash_is_the_parents():
     from microaligner_amd import build
-    assert build.source_hash() == "c8c3e3bfcfe3f943" == _lib.source_hash()
+    assert build.source_hash() == HASH == _lib.source_hash()
     assert "flow_refine.hip" in build.SOURCES and "microaligner_flowrefine.h" not in " ".join(build.HEADERS)
     assert [os.path.basename(h) for h in build.SOURCE_HEADERS["flow_refine.hip"]] == ["microaligner_flowrefine.h",
                                                                                       "microaligner_flowsmooth.h",

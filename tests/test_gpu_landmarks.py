@@ -12,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _landmarks_ref as R  # noqa: E402
+from _measured_path import HASH  # noqa: E402
 from microaligner_amd import FlowGrid, Warper, _lib, fit_landmarks, landmark_flow, landmark_points, transform_points  # noqa: E402
 from microaligner_amd.device import DeviceArray  # noqa: E402
 
@@ -307,5 +308,5 @@ def test_c_entries_refuse_bad_arguments_without_launching(ctx):
 
 def test_the_loaded_library_is_this_trees():
     from microaligner_amd import build
-    assert _lib.source_hash() == build.source_hash() == "c8c3e3bfcfe3f943"
+    assert _lib.source_hash() == build.source_hash() == HASH
     assert hasattr(_lib.load(), "ma_landmark_flow") and hasattr(_lib.load(), "ma_landmark_points")

@@ -12,6 +12,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _flow_smooth_ref as S  # noqa: E402
 import _local_correlation_ref as R  # noqa: E402
+from _measured_path import HASH  # noqa: E402
 from microaligner_amd import CorrelationMaps, FlowGrid, _lib, fit_flow_affine, local_correlation, smooth_flow  # noqa: E402
 from microaligner_amd.device import DeviceArray, grid_nodes  # noqa: E402
 from test_gpu_flow_invert import same_bits  # noqa: E402
@@ -304,4 +305,4 @@ def test_the_library_exports_the_entry_and_carries_the_parents_hash():
     from microaligner_amd import build
     lib = _lib.load()
     assert hasattr(lib, "ma_local_correlation"), "ma_local_correlation declared in microaligner_localcorr.h but not exported"
-    assert build.source_hash() == "c8c3e3bfcfe3f943" == _lib.source_hash()
+    assert build.source_hash() == HASH == _lib.source_hash()

@@ -1,9 +1,9 @@
 """-m gpu: the local contrast normalisation on the device.  ma_normalize_local against the numpy float32 statement of
 include/microaligner_localnorm.h (tests/_local_norm_ref.py) bit for bit, its counts exactly; normalize_local() end to end;
-refused arguments at the C entry.  The refusals below the alignment rule and the registry cases (stale scratch memory,
-shifted addresses) are in tests/test_gpu_unaligned_local_norm.py.
+refused arguments at the C entry.  The refusals below the alignment rule are in tests/test_gpu_unaligned.py, the registry
+cases (stale scratch memory, shifted addresses) in tests/_gpu_cases/local_norm.py.
 
-Observed on an MI355X: every case gives the statement's bits and counts; the two files together take 2.1 s."""
+Observed on an MI355X: every case gives the statement's bits and counts; the file takes 1.8 s."""
 import ctypes as C
 import os
 import sys
@@ -14,6 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _flow_smooth_ref as S  # noqa: E402
 import _local_norm_ref as R  # noqa: E402
+from _measured_path import HASH  # noqa: E402
 from microaligner_amd import LocalNormInfo, _lib, normalize_local  # noqa: E402
 from microaligner_amd.device import DeviceArray  # noqa: E402
 from test_gpu_flow_smooth import taps_of  # noqa: E402
@@ -261,4 +262,4 @@ def test_the_library_exports_the_entry_and_carries_the_parents_hash():
     from microaligner_amd import build
     lib = _lib.load()
     assert hasattr(lib, "ma_normalize_local"), "ma_normalize_local declared in microaligner_localnorm.h but not exported"
-    assert build.source_hash() == "c8c3e3bfcfe3f943" == _lib.source_hash()
+    assert build.source_hash() == HASH == _lib.source_hash()

@@ -12,6 +12,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _flow_affine_ref as A  # noqa: E402
 import _texture_ref as T  # noqa: E402
+from _measured_path import HASH  # noqa: E402
 from microaligner_amd import TextureMaps, _lib, fit_flow_affine, texture_maps  # noqa: E402
 from microaligner_amd.device import DeviceArray  # noqa: E402
 from test_gpu_flow_affine import E2E_TOL  # noqa: E402
@@ -237,7 +238,7 @@ def test_header_library_and_bindings_agree():
 
 def test_the_source_hash_is_the_parents():
     from microaligner_amd import build
-    assert build.source_hash() == "c8c3e3bfcfe3f943" == _lib.source_hash()
+    assert build.source_hash() == HASH == _lib.source_hash()
     assert "texture.hip" in build.SOURCES and "microaligner_texture.h" not in " ".join(build.HEADERS)
     assert [os.path.basename(h) for h in build.SOURCE_HEADERS["texture.hip"]] == ["microaligner_texture.h", "cell_grid.h",
                                                                                   "window_fir.h"]

@@ -6,11 +6,11 @@ pointers"): aligned to its element; an array of pairs (flows, maps, grid nodes, 
 header names an argument.  Within the rule every result is the same as at an aligned address; below it an entry returns
 MA_EINVAL before it launches anything.
 
-The first half runs the registry of tests/test_gpu_stale_memory.py again.  Every case builds its inputs and its expected
-result once and runs its call three times: with the plain allocator, and twice with Context.empty replaced by one that
-allocates 64 bytes more, fills the whole allocation with 0xFF and hands out a view at an offset inside it (Context._upload_raw
-likewise, by the shape and type of the array it uploads; Context._raw, whose untyped bytes a call fills with int32, float64 or
-pairs of float64, by the strictest of those) --
+The first half runs the registry of tests/_gpu_cases, as tests/test_gpu_stale_memory.py does.  Every case builds its inputs
+and its expected result once and runs its call three times: with the plain allocator, and twice with Context.empty replaced
+by one that allocates 64 bytes more, fills the whole allocation with 0xFF and hands out a view at an offset inside it
+(Context._upload_raw likewise, by the shape and type of the array it uploads; Context._raw, whose untyped bytes a call fills
+with int32, float64 or pairs of float64, by the strictest of those) --
 
   edge : the address is = A (mod 16) for an array whose alignment under the rule is A <= 8, = 16 (mod 32) for A = 16,
          = 32 (mod 64) for A = 32: as far off every larger boundary as the rule allows;
@@ -30,15 +30,18 @@ The second half calls every checked entry below the rule: REJECT lists (entry, p
 that a kernel reads or writes through a wider type than it is declared with (MA_REQUIRE_ALIGNED in the sources); CALLS holds
 valid arguments of a small legal size for each entry.  With that one pointer bytes / 2 past an aligned address the entry must
 return MA_EINVAL and name the parameter in ma_last_error(); the same call with the pointer put back must succeed, which it
-would not after a launch on a misaligned record or with a profile scope left open.
+would not after a launch on a misaligned record or with a profile scope left open.  Where an entry checks an argument against
+the size of its element (ELEMENT_SIZED: ma_normalize_local), BELOW lists the pointers below that, and a uint8 array is shown
+to have no such address.
 
-tests/test_unaligned_tables.py (no GPU) checks offset_for and holds REJECT, CALLS and OVERRIDES against the headers.
+tests/test_unaligned_tables.py (no GPU) checks offset_for and holds REJECT, CALLS, OVERRIDES, BELOW and ELEMENT_SIZED against
+the headers and the sources.
 
-Observed on an MI355X: all 87 cases give the bits of the plain run at both sets of addresses, the float64 sums of
+Observed on an MI355X: all 89 cases give the bits of the plain run at both sets of addresses, the float64 sums of
 ma_flow_affine_moments apart.  With joint_hist16_kernel's scalar loop made wrong where its vector arm is switched off
 (`count(a[i], b[i + (vec_ok ? 0 : 1)])`, nmi.hip) the two nmi_scores cases and the two feature_round cases of this file fail,
 against the statement and against the plain run, while the same cases of tests/test_gpu_stale_memory.py pass: they never leave
-the vector arm.  The file takes 9.2 s where the stale-memory file takes 8.3 s."""
+the vector arm.  The file takes 7.7 s where the stale-memory file takes 8.8 s (89 cases each, the second half included)."""
 import ctypes as C
 import os
 import sys
@@ -48,7 +51,10 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import test_gpu_stale_memory as S       # noqa: E402  (the registry: CASES, Env, assert_same)
+pytest.register_assert_rewrite("_gpu_cases")       # the cases' own asserts are quoted by run_shifted: keep them informative
+import _gpu_cases as G  # noqa: E402  (the registry: CASES, Env, assert_same)
+from _gpu_cases.dog import _DT  # noqa: E402
+from _gpu_cases.pyramid import _image  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F32, F64 = np.float32, np.float64
@@ -243,13 +249,13 @@ def run_shifted(ctx, monkeypatch, env, c):
             if callable(expected):
                 expected(res)
             else:
-                S.assert_same(res, expected, name[k])
+                G.assert_same(res, expected, name[k])
         except AssertionError as e:
             failed.append(f"{name[k]}: against the statement: {str(e).splitlines()[0] if str(e) else repr(e)}")
         if c.bits and k:
             part = BIT_EXEMPT[c.name][1] if c.name in BIT_EXEMPT else (lambda r: r)
             try:
-                S.assert_same(part(res), part(results[0]), name[k])
+                G.assert_same(part(res), part(results[0]), name[k])
             except AssertionError as e:
                 failed.append(f"{name[k]}: against the plain run: {str(e).splitlines()[0] if str(e) else repr(e)}")
     assert not failed, f"{len(failed)} checks failed:\n" + "\n".join(failed)
@@ -257,22 +263,22 @@ def run_shifted(ctx, monkeypatch, env, c):
 
 @pytest.fixture(scope="module")
 def env(ctx, tmp_path_factory):
-    return S.Env(ctx, tmp_path_factory)
+    return G.Env(ctx, tmp_path_factory)
 
 
-@pytest.mark.parametrize("c", S.CASES, ids=[c.name for c in S.CASES])
+@pytest.mark.parametrize("c", G.CASES, ids=[c.name for c in G.CASES])
 def test_call_at_shifted_addresses(ctx, env, monkeypatch, c):
     run_shifted(ctx, monkeypatch, env, c)
 
 
 def test_the_tables_name_cases_and_entries_of_the_registry():
-    names = {c.name for c in S.CASES}
+    names = {c.name for c in G.CASES}
     assert set(OVERRIDES) <= names and set(BIT_EXEMPT) <= names
-    assert set(ALIGNED16) <= S.declared_entries()
+    assert set(ALIGNED16) <= G.declared_entries()
     for table in (OVERRIDES, BIT_EXEMPT):
         for key, (_, *rest) in table.items():
             assert all(rest), key
-    for c in S.CASES:
+    for c in G.CASES:
         if c.name in BIT_EXEMPT:
             assert c.bits, c.name
     assert all(isinstance(r, str) and r.strip() for r in ALIGNED16.values())
@@ -288,21 +294,21 @@ def test_the_tables_name_cases_and_entries_of_the_registry():
 def test_pyr_down_with_a_width_of_the_vector_arm_at_an_element_aligned_address(ctx, dtype, moved):
     from microaligner_amd.device import Context
     h, w = 64, 2052
-    img = S._image((h, w), dtype, 71)
-    exp = S._O().pyr_down(img)
+    img = _image((h, w), dtype, 71)
+    exp = G._O().pyr_down(img)
     ctx._resident.clear()
     plain = ctx.pyr_down(ctx.asdevice(img)).numpy()
-    S.assert_same(plain, exp, "at aligned addresses")
+    G.assert_same(plain, exp, "at aligned addresses")
     size = np.dtype(dtype).itemsize
     alloc = Shifted(ctx, "edge", None, Context.empty)
     src = alloc.view((h, w), dtype, size if moved != "dst" else 16)
     dst = alloc.view(exp.shape, dtype, size if moved != "src" else 16)
     from microaligner_amd import _lib as L
     L.check(ctx.lib.ma_memcpy_h2d(ctx.handle, src.ptr, img.ctypes.data, img.nbytes))
-    ctx._run(ctx.lib.ma_pyr_down, src.ptr, S._DT[np.dtype(dtype)], h, w, dst.ptr)
+    ctx._run(ctx.lib.ma_pyr_down, src.ptr, _DT[np.dtype(dtype)], h, w, dst.ptr)
     got = dst.numpy()
     ctx._resident.clear()
-    S.assert_same(got, exp, f"{moved} moved by {size}")
+    G.assert_same(got, exp, f"{moved} moved by {size}")
     assert not alloc.slack_damage()
 
 
@@ -391,7 +397,7 @@ class Bufs:
         self.pages, self.outs = (C.c_void_p * 1)(self.page.ctypes.data), (C.c_void_p * 1)(self.page_out.ctypes.data)
         self.d, self.ll, self.ll2, self.f = (C.c_double * 16)(), (C.c_longlong * 16)(), (C.c_longlong * 16)(), (C.c_float * 16)()
         self.d2, self.d3 = (C.c_double * 16)(), (C.c_double * 16)()
-        ref, mov = S.pair(*REG, seed=1)
+        ref, mov = G.pair(*REG, seed=1)
         self.ref, self.mov = ctx.asdevice(ref), ctx.asdevice(mov)
         self.reg_flow = ctx.empty(REG + (2,), F32)
         from microaligner_amd import _lib as L
@@ -461,3 +467,72 @@ def test_a_pointer_below_the_rule_is_refused_before_any_launch(ctx, bufs, entry,
     rc = fn(ctx.handle, *good)
     assert rc == L.MA_OK, (rc, ctx.lib.ma_last_error().decode())
     ctx.sync()
+
+
+# ---- below the rule, where the check is the size of the element ----------------------------------------------------------------
+# (source file, parameter, the size as the source writes it): every MA_REQUIRE_ALIGNED whose size is no literal.  The size
+# follows an argument of the call, so REJECT's one row per parameter cannot hold it; BELOW lists the pointers instead.
+ELEMENT_SIZED = [
+    ("local_norm.hip", "img", "img_elem"),
+    ("local_norm.hip", "weight", "weight_elem"),
+    ("local_norm.hip", "out_f32", "sizeof(float)"),
+]
+
+# (parameter, dtype code of the image, weight kind, bytes of the element, what the pointer is moved by)
+BELOW = [("img", 1, 0, 2, 1), ("img", 2, 0, 4, 1), ("img", 2, 0, 4, 2), ("weight", 0, 1, 4, 1), ("weight", 0, 1, 4, 2),
+         ("out_f32", 0, 0, 4, 1), ("out_f32", 0, 0, 4, 2)]
+
+
+def below_call(p, dtype, kind, taps, counts):
+    """the arguments after ctx of a valid ma_normalize_local on an N x N image, by the names BELOW uses, in the order of the
+    prototype; p: four device pointers (the image, the weight, the two outputs)"""
+    return dict(img=p[0], dtype=dtype, H=N, W=N, taps=taps, r=1, floor=1.0, clip=4.0, weight=p[1] if kind else None,
+                kind=kind, ms=0.0, out_f32=p[2], out_u8=p[3], counts=counts)
+
+
+@pytest.mark.parametrize("param,dtype,kind,nbytes,by", BELOW, ids=[f"{p}:{n}-byte element + {b}" for p, _, _, n, b in BELOW])
+def test_a_pointer_below_the_rule_is_refused_before_any_launch_element_sized(ctx, param, dtype, kind, nbytes, by):
+    from microaligner_amd import _lib as L
+    z = [ctx.zeros((16384,), F32) for _ in range(4)]
+    sentinel = np.full(N * N, 7, F32)
+    L.check(ctx.lib.ma_memcpy_h2d(ctx.handle, z[2].ptr, sentinel.ctypes.data, sentinel.nbytes))
+    taps = (C.c_float * 2)(0.5, 0.25)
+    counts = (C.c_longlong * 4)(-1, -1, -1, -1)
+    good = below_call([a.ptr for a in z], dtype, kind, taps, counts)
+    bad = dict(good)
+    bad[param] = good[param] + by
+    rc = ctx.lib.ma_normalize_local(ctx.handle, *bad.values())
+    msg = ctx.lib.ma_last_error().decode()
+    assert rc == L.MA_EINVAL, (rc, msg)
+    assert f"{param} must be {nbytes}-byte aligned" in msg, msg
+    assert tuple(counts) == (-1, -1, -1, -1)
+    ctx.sync()
+    assert np.array_equal(z[2].numpy()[:N * N], sentinel)                # nothing was launched
+    rc = ctx.lib.ma_normalize_local(ctx.handle, *good.values())
+    assert rc == L.MA_OK, (rc, ctx.lib.ma_last_error().decode())
+    # an all-zero image: every pixel is live, supported unless its weight is 0 (the all-zero weight), flat and 128
+    assert tuple(counts) == ((N * N, 0, 0, 0) if kind else (0, 0, N * N, 0))
+    assert (z[3].numpy().view(np.uint8)[:N * N] == 128).all() and not z[2].numpy()[:N * N].any()
+
+
+@pytest.mark.parametrize("which", ["out_u8", "mask", "img"])
+def test_a_uint8_array_has_no_address_below_the_rule(ctx, which):
+    """at an odd address a uint8 image, mask or output is within the rule, and the result is the statement's"""
+    import _local_norm_ref as R
+    from microaligner_amd import _lib as L
+    from test_gpu_flow_smooth import taps_of
+    SHAPE = G.SHAPE
+    img = R.make_image(*SHAPE, np.uint8)
+    mask = R.make_weight(*SHAPE)[1]
+    taps, floor = taps_of(7), R.floor_of(np.uint8)
+    exp = R.normalize_local_ref(img, taps, floor, 4.0, mask, 0.05)
+    alloc = Shifted(ctx, "edge", None, type(ctx).empty)
+    d_img, d_mask, out = (alloc.view(SHAPE, np.uint8, 1 if which == n else 16) for n in ("img", "mask", "out_u8"))
+    for d, a in ((d_img, img), (d_mask, mask)):
+        L.check(ctx.lib.ma_memcpy_h2d(ctx.handle, d.ptr, a.ctypes.data, a.nbytes))
+    counts = (C.c_longlong * 4)()
+    ctx._run(ctx.lib.ma_normalize_local, d_img.ptr, L.MA_U8, *SHAPE, taps.ctypes.data_as(C.POINTER(C.c_float)), 7, floor, 4.0,
+             d_mask.ptr, L.MA_SMOOTH_WEIGHT_U8, 0.05, None, out.ptr, counts)
+    assert (d_img.ptr if which == "img" else d_mask.ptr if which == "mask" else out.ptr) % 2 == 1
+    G.assert_same((out.numpy(), tuple(counts)), (exp["u8"], exp["counts"]), which)
+    assert not alloc.slack_damage()

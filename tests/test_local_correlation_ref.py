@@ -12,6 +12,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _flow_smooth_ref as S  # noqa: E402
 import _local_correlation_ref as R  # noqa: E402
+from _measured_path import HASH  # noqa: E402
 
 F32, F64 = np.float32, np.float64
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -249,7 +250,7 @@ def test_header_and_bindings_agree():
 
 def test_the_source_is_built_and_off_the_measured_path():
     from microaligner_amd import build
-    assert build.source_hash() == "c8c3e3bfcfe3f943"
+    assert build.source_hash() == HASH
     assert "local_correlation.hip" in build.SOURCES and "microaligner_localcorr.h" not in " ".join(build.HEADERS)
     assert [os.path.basename(h) for h in build.SOURCE_HEADERS["local_correlation.hip"]] == \
         ["microaligner_localcorr.h", "microaligner_flowsmooth.h", "cell_grid.h", "window_fir.h", "weight_map.h"]

@@ -12,6 +12,10 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _flow_smooth_ref as S  # noqa: E402
 import _local_norm_ref as R  # noqa: E402
+from _measured_path import HASH  # noqa: E402
+
+pytest.register_assert_rewrite("_gpu_cases")
+import _gpu_cases as G  # noqa: E402  (the registry: CASES, EXEMPT, declared_entries)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "microaligner_localnorm.h")
@@ -178,7 +182,7 @@ def test_header_exports_and_bindings_agree():
 
 def test_the_source_is_built_and_off_the_measured_path():
     from microaligner_amd import build
-    assert build.source_hash() == "c8c3e3bfcfe3f943"
+    assert build.source_hash() == HASH
     assert "local_norm.hip" in build.SOURCES and "microaligner_localnorm.h" not in " ".join(build.HEADERS)
     assert [os.path.basename(h) for h in build.SOURCE_HEADERS["local_norm.hip"]] == \
         ["microaligner_localnorm.h", "microaligner_flowsmooth.h", "window_fir.h", "weight_map.h", "call_counts.h"]
@@ -187,6 +191,12 @@ def test_the_source_is_built_and_off_the_measured_path():
     src = open(os.path.join(build.CSRC, "local_norm.hip")).read()
     for word in ("wf_row_plane", "wf_acquire", "wf_finish", "wf_taps", "d_weight_px", "ma_weight_check", "d_wave_tally"):
         assert word in src, word
+
+
+def test_the_cases_are_in_the_registry():
+    """the GPU cases that run ma_normalize_local on stale scratch memory and at shifted addresses (tests/_gpu_cases)"""
+    cases = [c for c in G.CASES if c.entries == ("ma_normalize_local",)]
+    assert len(cases) == 2 and "ma_normalize_local" in G.declared_entries() and "ma_normalize_local" not in G.EXEMPT
 
 
 # ---- refused arguments -----------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """The tables of tests/test_gpu_unaligned.py without a GPU: the offsets of the shifted allocator, and that every entry and
-parameter the rejection and override tables name is one of the headers and of the bindings."""
+parameter the rejection and override tables name is one of the headers and of the bindings, and that the tables account for
+every alignment check of the sources."""
 import ctypes as C
 import glob
 import os
@@ -10,6 +11,10 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+pytest.register_assert_rewrite("_gpu_cases")
+import _gpu_cases  # noqa: E402  (the registry: declared_entries)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -86,7 +91,7 @@ def test_every_rejected_parameter_is_one_of_the_headers_and_of_the_bindings():
         assert protos[entry][0] == "ctx" and protos[entry][pos] == param, (entry, param, protos[entry])
         assert sigs[entry][1][pos] is C.c_void_p, (entry, param)
         assert nbytes in (8, 16, 32)
-        assert entry in U.CALLS and entry in S_declared(), entry
+        assert entry in U.CALLS and entry in _gpu_cases.declared_entries(), entry
     assert set(U.CALLS) == {e for e, _, _, _ in U.REJECT}
     # the valid calls have the arguments of the prototypes, each of a type its ctypes prototype converts
     from types import SimpleNamespace as NS
@@ -105,25 +110,54 @@ def test_every_rejected_parameter_is_one_of_the_headers_and_of_the_bindings():
     for entry, param, nbytes, pos in U.REJECT:
         a = U.CALLS[entry](b)[pos - 1]
         assert isinstance(a, int) and a % 64 == 0 and a >= 1 << 16, (entry, param)
-
-
-def S_declared():
-    import test_gpu_stale_memory as S
-    return S.declared_entries()
+    # the valid call of BELOW likewise: ma_normalize_local, each moved parameter at the position of its name in the prototype
+    entry = "ma_normalize_local"
+    assert entry in protos and entry in sigs and entry in _gpu_cases.declared_entries() and entry not in U.CALLS
+    assert len(set(U.BELOW)) == len(U.BELOW)
+    for param, dtype, kind, nbytes, by in U.BELOW:
+        good = U.below_call(b.p[:4], dtype, kind, b.taps, (C.c_longlong * 4)())
+        args, types = list(good.values()), sigs[entry][1][1:]
+        assert len(args) == len(types) == len(protos[entry]) - 1
+        for k, (a, t) in enumerate(zip(args, types)):
+            t.from_param(a)
+            if t is C.c_int:
+                assert isinstance(a, int) and abs(a) < 1 << 16, (entry, k, a)
+        pos = 1 + list(good).index(param)
+        assert protos[entry][0] == "ctx" and protos[entry][pos] == param and sigs[entry][1][pos] is C.c_void_p, (param, pos)
+        assert isinstance(good[param], int) and good[param] % 64 == 0 and good[param] >= 1 << 16, param
+        # the element at that pointer in this call has nbytes bytes, and the pointer moved by `by` is not a multiple of it
+        element = {"img": {L.MA_U8: 1, L.MA_U16: 2, L.MA_F32: 4}[dtype], "weight": 4 if kind == L.MA_SMOOTH_WEIGHT_F32 else 1,
+                   "out_f32": 4}[param]
+        assert nbytes == element and 0 < by < nbytes
 
 
 def test_every_checked_parameter_of_the_sources_is_in_the_rejection_table():
-    """MA_REQUIRE_ALIGNED(ptr, bytes, "name") in an entry of csrc/ <-> a row of REJECT: nothing checked is left untested, and
-    the table names nothing the sources do not check"""
+    """every MA_REQUIRE_ALIGNED(ptr, size, "name") in an entry of csrc/ is accounted for: with a literal size <-> a row of
+    REJECT; with any other size <-> a row of ELEMENT_SIZED, whose parameters are those of BELOW.  Nothing checked is left
+    untested, and the tables name nothing the sources do not check"""
     import test_gpu_unaligned as U
     csrc = os.path.join(ROOT, "microaligner_amd", "csrc")
-    found = set()
+    uses, literal, found, sized = 0, 0, set(), []
     for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
-        for m in re.finditer(r"MA_REQUIRE_ALIGNED\((\w+), (\d+), \"(\w+)\"\)", open(path).read()):
+        text = open(path).read()
+        uses += len(re.findall(r"MA_REQUIRE_ALIGNED\s*\(", text))
+        for m in re.finditer(r"MA_REQUIRE_ALIGNED\((\w+), ([^;\n]+?), \"(\w+)\"\)", text):
             assert m.group(1) == m.group(3), (path, m.group(0))
-            found.add((os.path.basename(path), m.group(3), int(m.group(2))))
+            if re.fullmatch(r"\d+", m.group(2)):
+                literal += 1
+                found.add((os.path.basename(path), m.group(3), int(m.group(2))))
+            else:
+                sized.append((os.path.basename(path), m.group(3), m.group(2)))
     table = {(p, n) for _, p, n, _ in U.REJECT}
     assert {(p, n) for _, p, n in found} == table, ({(p, n) for _, p, n in found} ^ table)
+    assert sorted(sized) == sorted(U.ELEMENT_SIZED), (sized, U.ELEMENT_SIZED)
+    assert {p for _, p, _ in U.ELEMENT_SIZED} == {p for p, _, _, _, _ in U.BELOW}
+    # BELOW moves each of them, at every element size above one byte that it can have, by an odd number of bytes and by an
+    # even one that is no multiple of the element
+    sizes = {"img": (2, 4), "weight": (4,), "out_f32": (4,)}
+    assert sorted((p, n, by) for p, _, _, n, by in U.BELOW) == sorted((p, n, by) for p, ns in sizes.items() for n in ns
+                                                                      for by in (1, 2) if by < n)
+    assert literal + len(sized) == uses, (literal, len(sized), uses)       # no use that neither pattern reads
     helper = open(os.path.join(csrc, "ma_internal.h")).read()
     assert "#define MA_REQUIRE_ALIGNED(ptr, bytes, name)" in helper and "must be %d-byte aligned" in helper
     # no hand-written alignment refusal is left beside the helper
