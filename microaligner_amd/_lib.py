@@ -299,6 +299,13 @@ LOCALNORM_SIGNATURES = {
                                 C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_morphology.h (flat grey morphology of an image)
+MA_MORPH_ERODE, MA_MORPH_DILATE, MA_MORPH_OPEN, MA_MORPH_CLOSE, MA_MORPH_TOPHAT, MA_MORPH_BLACKHAT = 0, 1, 2, 3, 4, 5   # enum ma_morph_op
+MA_MORPH_MAX_RADIUS = 255
+MORPH_SIGNATURES = {
+    "ma_morphology": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+}
+
 # name -> (restype, argtypes): exactly the symbols of include/microaligner_debug.h (test hook: fill idle scratch memory)
 DEBUG_SIGNATURES = {
     "ma_debug_fill_idle": (_i, [_vp, _i, C.POINTER(C.c_ulonglong)]),
@@ -324,7 +331,8 @@ def load():
             list(DIRECT_SIGNATURES.items()) + list(FLOWREFINE_SIGNATURES.items()) + \
             list(LANDMARK_SIGNATURES.items()) + list(TRANSLATION_SIGNATURES.items()) + \
             list(QUANTILE_SIGNATURES.items()) + list(LOCALCORR_SIGNATURES.items()) + list(FLOWMEDIAN_SIGNATURES.items()) + \
-            list(FLOWFILL_SIGNATURES.items()) + list(LOCALNORM_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
+            list(FLOWFILL_SIGNATURES.items()) + list(LOCALNORM_SIGNATURES.items()) + list(MORPH_SIGNATURES.items()) + \
+            list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -498,6 +498,33 @@ def local_norm_params(img, taps, floor, clip=4.0, weight=None, min_support=0.0, 
     return H, W, dtype, taps, r, floor, c, kind, ms, tuple(want)
 
 
+# ---- flat grey morphology of an image (include/microaligner_morphology.h) ---------------------------------------------------
+MORPH_OPS = {"erode": L.MA_MORPH_ERODE, "dilate": L.MA_MORPH_DILATE, "open": L.MA_MORPH_OPEN, "close": L.MA_MORPH_CLOSE,
+             "tophat": L.MA_MORPH_TOPHAT, "blackhat": L.MA_MORPH_BLACKHAT}
+
+
+def morphology_params(img, op, radius):
+    """Checks and host-side arguments of the flat grey morphology (include/microaligner_morphology.h) without touching a
+    device: (H, W, dtype code, op code, ry, rx).  img: an (H, W) uint8, uint16 or float32 array (numpy or device), not
+    empty; op: one of "erode", "dilate", "open", "close", "tophat", "blackhat"; radius: an int, or (ry, rx), each an int
+    in 0 .. 255 (the rectangle has (2 ry + 1) x (2 rx + 1) pixels).  ValueError for anything the C entry would refuse."""
+    dtype = _check_image(img, "img")
+    H, W = (int(v) for v in img.shape)
+    _image_sides(H, W)
+    if not isinstance(op, str) or op not in MORPH_OPS:
+        raise ValueError(f"op must be one of {sorted(MORPH_OPS)}, got {op!r}")
+    rr = radius
+    if isinstance(rr, (int, np.integer)) and not isinstance(rr, (bool, np.bool_)):
+        rr = (rr, rr)
+    if not isinstance(rr, (tuple, list)) or len(rr) != 2 or \
+            any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in rr):
+        raise ValueError(f"radius must be an int or a pair of ints (ry, rx), got {radius!r}")
+    ry, rx = (int(v) for v in rr)
+    if not (0 <= ry <= L.MA_MORPH_MAX_RADIUS and 0 <= rx <= L.MA_MORPH_MAX_RADIUS):
+        raise ValueError(f"a radius must be in [0, {L.MA_MORPH_MAX_RADIUS}], got {radius!r}")
+    return H, W, dtype, MORPH_OPS[op], ry, rx
+
+
 # ---- global translation search (include/microaligner_translation.h) --------------------------------------------------------
 def translation_params(ref, mov, window, exclude=0):
     """Checks and host-side arguments of the translation search (include/microaligner_translation.h) without touching a
@@ -1707,6 +1734,21 @@ class Context:
         self._run(self.lib.ma_normalize_local, img.ptr, dtype, H, W, taps.ctypes.data_as(C.POINTER(C.c_float)), r, floor, clip,
                   None if weight is None else weight.ptr, kind, ms, ptr["f32"], ptr["u8"], counts if return_info else None)
         return (out, LocalNormInfo(*(int(v) for v in counts))) if return_info else out
+
+    def morphology(self, img, op, radius, out=None):
+        """The flat grey morphology of an (H, W) uint8, uint16 or float32 device image over the rectangle of
+        (2 ry + 1) x (2 rx + 1) pixels, radius = r or (ry, rx), each 0 .. 255 (include/microaligner_morphology.h): op
+        "erode" / "dilate" the smallest / largest value of the window cut at the border, "open" = dilate(erode),
+        "close" = erode(dilate), "tophat" = img - open, "blackhat" = close - img.  Exact: every result but a hat's is one of
+        the input values; float32 NaNs take no part in a window.  A new device array of img's dtype out; `out` may name the
+        array to write instead, `img` itself included."""
+        H, W, dtype, code, ry, rx = morphology_params(img, op, radius)
+        if out is None:
+            out = self.empty((H, W), img.dtype)
+        elif not isinstance(out, DeviceArray) or out.dtype != img.dtype or out.shape != (H, W):
+            raise ValueError(f"out must be a {np.dtype(img.dtype)} DeviceArray of shape {(H, W)}")
+        self._run(self.lib.ma_morphology, img.ptr, dtype, H, W, code, ry, rx, out.ptr)
+        return out
 
     def flow_refine_step(self, ref, warped, flow, taps, floor, weight=None, max_step=1.0, return_info=False, out=None):
         """One regularised Lucas-Kanade step of `flow` (include/microaligner_flowrefine.h): the 2 x 2 system of the
