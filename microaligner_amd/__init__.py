@@ -19,6 +19,7 @@ from .shared_modules.texture import TextureMaps, texture_maps
 from .shared_modules.local_correlation import CorrelationMaps, local_correlation
 from .shared_modules.normalize import LocalNormInfo, NormalizeInfo, normalize_local, normalize_percentile
 from .shared_modules.morphology import grey_close, grey_dilate, grey_erode, grey_open, tophat
+from .shared_modules.components import ComponentInfo, fill_holes, label_components, remove_small_objects
 from .shared_modules.utils import max_project_and_normalize, pad_to_shape, transform_img_with_tmat
 
 __all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc", "farneback", "merge_two_flows", "compose_flows", "invert_flow", "transform_points", "pad_to_shape",
@@ -29,5 +30,6 @@ __all__ = ["FeatureRegistrator", "OptFlowRegistrator", "Warper", "TileFlowCalc",
            "LandmarkFit", "fit_landmarks", "landmark_flow", "landmark_points", "align_translation", "TranslationInfo",
            "normalize_percentile", "NormalizeInfo", "local_correlation", "CorrelationMaps", "median_flow", "outlier_mask",
            "MedianInfo", "fill_flow", "FillInfo", "normalize_local", "LocalNormInfo",
-           "grey_erode", "grey_dilate", "grey_open", "grey_close", "tophat"]
+           "grey_erode", "grey_dilate", "grey_open", "grey_close", "tophat",
+           "label_components", "remove_small_objects", "fill_holes", "ComponentInfo"]
 __version__ = "0.1.0"

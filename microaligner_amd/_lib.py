@@ -306,6 +306,17 @@ MORPH_SIGNATURES = {
     "ma_morphology": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
+# name -> (restype, argtypes): exactly the symbols of include/microaligner_components.h (connected components of an image)
+MA_CC_I32 = 3                                           # the dtype code of an int32 image, beside MA_U8 and MA_U16
+MA_CC_MAX_PIXELS = 2147483647
+MA_CC_TILE = 64
+MA_CC_CONN8, MA_CC_BY_VALUE, MA_CC_HOLES = 1, 2, 4      # enum ma_cc_flags
+COMPONENTS_SIGNATURES = {
+    "ma_cc_label": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(C.c_longlong)]),
+    "ma_cc_stats": (_i, [_vp, _vp, _i, _i, C.c_longlong, _vp, _vp]),
+    "ma_cc_filter": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong, _vp]),
+}
+
 # name -> (restype, argtypes): exactly the symbols of include/microaligner_debug.h (test hook: fill idle scratch memory)
 DEBUG_SIGNATURES = {
     "ma_debug_fill_idle": (_i, [_vp, _i, C.POINTER(C.c_ulonglong)]),
@@ -332,7 +343,7 @@ def load():
             list(LANDMARK_SIGNATURES.items()) + list(TRANSLATION_SIGNATURES.items()) + \
             list(QUANTILE_SIGNATURES.items()) + list(LOCALCORR_SIGNATURES.items()) + list(FLOWMEDIAN_SIGNATURES.items()) + \
             list(FLOWFILL_SIGNATURES.items()) + list(LOCALNORM_SIGNATURES.items()) + list(MORPH_SIGNATURES.items()) + \
-            list(DEBUG_SIGNATURES.items()):
+            list(COMPONENTS_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the C-ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libmicroaligner_hip.so")
 SOURCES = ["ma_api.hip", "farneback.hip", "remap.hip", "pyramid.hip", "dog.hip", "nmi.hip", "affine.hip", "knn.hip", "daisy.hip", "ransac.hip", "feature_round.hip", "register.hip", "probe.hip", "qc.hip", "remap_interp.hip", "warp_compose.hip", "page_pipeline.hip",
            "flow_compose.hip", "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip", "texture.hip", "direct_affine.hip", "flow_refine.hip",
            "landmarks.hip", "translation.hip", "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip", "debug_fill.hip",
-           "local_norm.hip", "morphology.hip"]
+           "local_norm.hip", "morphology.hip", "components.hip"]
 
 
 def _inc(name):
@@ -62,7 +62,8 @@ SOURCE_HEADERS = {"qc.hip": [_inc("microaligner_qc.h"), _CELL_GRID, _FLOW_JACOBI
                   "flow_fill.hip": [_inc("microaligner_flowfill.h"), _SMOOTH_H, _WEIGHT_MAP, _CALL_COUNTS],
                   "debug_fill.hip": [_inc("microaligner_debug.h")],
                   "local_norm.hip": [_inc("microaligner_localnorm.h"), _SMOOTH_H, _WINDOW_FIR, _WEIGHT_MAP, _CALL_COUNTS],
-                  "morphology.hip": [_inc("microaligner_morphology.h")]}
+                  "morphology.hip": [_inc("microaligner_morphology.h")],
+                  "components.hip": [_inc("microaligner_components.h")]}
 # the grid-flow headers are also read by the two sources whose kernels take their flow from a grid: further dependencies of
 # those sources, beside the headers of their own above
 GRID_FLOW_USERS = {"warp_compose.hip": _FLOW_GRID, "flow_invert.hip": _FLOW_GRID}
@@ -131,6 +132,8 @@ def source_hash():
     #     only normalize_local() reaches;
     #   - the flat grey morphology (running minimum and maximum over a rectangle, opening, closing, top-hats), which only
     #     grey_erode() / grey_dilate() / grey_open() / grey_close() / tophat() reach;
+    #   - the connected components (labels, areas and boxes, the area filter and the hole filling), which only
+    #     label_components() / remove_small_objects() / fill_holes() reach;
     #   - the test hook that fills a context's idle scratch memory, which only tests call and which launches no kernel;
     #   - cell_grid.h, the cell grid and batch loop of the quality and residual shift maps, flow_jacobian.h, det J of
     #     the quality maps and the fold mask, window_fir.h, the separable FIR tile of the flow smoothing, the texture
@@ -142,7 +145,7 @@ def source_hash():
                 "flow_invert.hip", "residual_shift.hip", "flow_grid.hip", "flow_smooth.hip", "flow_affine.hip",
                 "texture.hip", "direct_affine.hip", "flow_refine.hip", "landmarks.hip", "translation.hip",
                 "quantile.hip", "local_correlation.hip", "flow_median.hip", "flow_fill.hip", "debug_fill.hip",
-                "local_norm.hip", "morphology.hip"}
+                "local_norm.hip", "morphology.hip", "components.hip"}
     for path in [os.path.join(CSRC, s) for s in SOURCES if s not in off_path] + HEADERS:
         h.update(open(path, "rb").read())
     h.update(" ".join(_flags()).encode())

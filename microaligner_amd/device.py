@@ -525,6 +525,62 @@ def morphology_params(img, op, radius):
     return H, W, dtype, MORPH_OPS[op], ry, rx
 
 
+# ---- connected components of an image (include/microaligner_components.h) ----------------------------------------------------
+CC_DTYPES = {np.dtype(np.uint8): L.MA_U8, np.dtype(np.uint16): L.MA_U16, np.dtype(np.int32): L.MA_CC_I32}
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def components_params(img, connectivity=1, by_value=False):
+    """Checks and host-side arguments of the connected components (include/microaligner_components.h) without touching a
+    device: (H, W, dtype code, flags).  img: an (H, W) uint8, uint16 or int32 array (numpy or device; a numpy bool array is
+    taken as uint8), 1 <= H, W <= 2^24 and H * W <= 2^31 - 1; connectivity: 1 (the 4 edge neighbours) or 2 (the 8
+    neighbours); by_value: a bool.  ValueError for anything the C entries would refuse."""
+    if not isinstance(img, (np.ndarray, DeviceArray)):
+        raise ValueError(f"img must be a numpy array or a DeviceArray, got {type(img).__name__}")
+    if len(img.shape) != 2:
+        raise ValueError(f"img: expected a 2D image, got shape {tuple(img.shape)}")
+    dtype = np.dtype(img.dtype)
+    if dtype == np.bool_ and isinstance(img, np.ndarray):
+        dtype = np.dtype(np.uint8)
+    if dtype not in CC_DTYPES:
+        raise ValueError(f"unsupported image dtype {dtype}: connected components take uint8, uint16, int32 or a bool mask "
+                         "(threshold a float image first)")
+    H, W = (int(v) for v in img.shape)
+    _image_sides(H, W)
+    if H * W > L.MA_CC_MAX_PIXELS:
+        raise ValueError(f"image too large: H * W must be at most 2^31 - 1, got {H} x {W}")
+    if not _is_int(connectivity) or connectivity not in (1, 2):
+        raise ValueError(f"connectivity must be 1 or 2, got {connectivity!r}")
+    if not isinstance(by_value, (bool, np.bool_)):
+        raise ValueError(f"by_value must be a bool, got {by_value!r}")
+    flags = (L.MA_CC_CONN8 if connectivity == 2 else 0) | (L.MA_CC_BY_VALUE if by_value else 0)
+    return H, W, CC_DTYPES[dtype], flags
+
+
+def remove_small_params(img, min_size, connectivity=1, by_value=False):
+    """components_params and min_size, an int >= 0: (H, W, dtype code, flags, min_size)."""
+    H, W, dtype, flags = components_params(img, connectivity, by_value)
+    if not _is_int(min_size) or min_size < 0:
+        raise ValueError(f"min_size must be an int >= 0, got {min_size!r}")
+    return H, W, dtype, flags, int(min_size)
+
+
+def fill_holes_params(img, max_size=None, connectivity=1, value=1):
+    """components_params, max_size (None or an int >= 0) and value (an int in 1 .. the largest value of img's dtype):
+    (H, W, dtype code, flags, max_area as the C entry reads it, value)."""
+    H, W, dtype, flags = components_params(img, connectivity, False)
+    if max_size is not None and (not _is_int(max_size) or max_size < 0):
+        raise ValueError(f"max_size must be None or an int >= 0, got {max_size!r}")
+    top = {L.MA_U8: 255, L.MA_U16: 65535, L.MA_CC_I32: 2 ** 31 - 1}[dtype]
+    if not _is_int(value) or not 1 <= value <= top:
+        raise ValueError(f"value must be an int in [1, {top}], got {value!r}")
+    max_area = L.MA_CC_MAX_PIXELS if max_size is None else min(int(max_size), L.MA_CC_MAX_PIXELS)
+    return H, W, dtype, flags | L.MA_CC_HOLES, max_area, int(value)
+
+
 # ---- global translation search (include/microaligner_translation.h) --------------------------------------------------------
 def translation_params(ref, mov, window, exclude=0):
     """Checks and host-side arguments of the translation search (include/microaligner_translation.h) without touching a
@@ -1748,6 +1804,83 @@ class Context:
         elif not isinstance(out, DeviceArray) or out.dtype != img.dtype or out.shape != (H, W):
             raise ValueError(f"out must be a {np.dtype(img.dtype)} DeviceArray of shape {(H, W)}")
         self._run(self.lib.ma_morphology, img.ptr, dtype, H, W, code, ry, rx, out.ptr)
+        return out
+
+    # connected components (include/microaligner_components.h) -----------------------------------------------------------
+    def components_asdevice(self, img):
+        """An image of the connected components on the device: a DeviceArray passes through, a numpy bool array is taken as
+        uint8, and a uint8, uint16 or int32 array is uploaded (asdevice() holds to the three image dtypes)."""
+        if isinstance(img, DeviceArray):
+            return img
+        arr = np.ascontiguousarray(img)
+        if arr.dtype == np.bool_:
+            arr = arr.view(np.uint8)
+        if arr.dtype != np.int32:
+            return self.asdevice(arr)
+        d = self.empty(arr.shape, np.int32)
+        if arr.nbytes:
+            L.check(self.lib.ma_memcpy_h2d(self.handle, d.ptr, arr.ctypes.data, arr.nbytes))
+        return d
+
+    def _cc_out(self, img, out, dtype):
+        H, W = img.shape
+        if out is None:
+            return self.empty((H, W), dtype)
+        if not isinstance(out, DeviceArray) or out.dtype != np.dtype(dtype) or out.shape != (H, W):
+            raise ValueError(f"out must be a {np.dtype(dtype)} DeviceArray of shape {(H, W)}")
+        return out
+
+    def label_components(self, img, connectivity=1, by_value=False, out=None):
+        """The connected components of an (H, W) uint8, uint16 or int32 device image (include/microaligner_components.h) ->
+        (labels, n): an int32 device array, 0 for background and k = 1 .. n for the component that is the k-th by its
+        smallest linear index y * W + x (scipy.ndimage.label's numbering), and the number of components.  A pixel is
+        foreground when it is not 0; connectivity 1 joins the 4 edge neighbours, 2 the 8 neighbours; by_value joins
+        neighbours only where their values are equal.  `out` may name the int32 array to write, but not `img`.  Waits for
+        the stream: n is a host value."""
+        H, W, dtype, flags = components_params(img, connectivity, by_value)
+        out = self._cc_out(img, out, np.int32)
+        if out is img:
+            raise ValueError("out must not be img")
+        n = C.c_longlong(-1)
+        self._run(self.lib.ma_cc_label, img.ptr, dtype, H, W, flags, out.ptr, C.byref(n))
+        return out, int(n.value)
+
+    def component_stats(self, labels, n):
+        """The areas and boxes of an (H, W) int32 device image of labels 0 .. n -> (areas, bboxes): device arrays of
+        (n + 1,) int64, areas[0] the background's, and (n + 1, 4) int32, y0, x0, y1, x1 with the ends exclusive, row 0 and
+        the rows of absent labels zeros.  Stream ordered."""
+        H, W, dtype, _ = components_params(labels)
+        if dtype != L.MA_CC_I32:
+            raise ValueError(f"labels must be int32, got {labels.dtype}")
+        if not _is_int(n) or not 0 <= n <= L.MA_CC_MAX_PIXELS - 1:
+            raise ValueError(f"n must be an int in [0, 2^31 - 2], got {n!r}")
+        areas, bboxes = self.empty((n + 1,), np.int64), self.empty((n + 1, 4), np.int32)
+        self._run(self.lib.ma_cc_stats, labels.ptr, H, W, int(n), areas.ptr, bboxes.ptr)
+        return areas, bboxes
+
+    def remove_small_objects(self, img, min_size, connectivity=1, by_value=False, out=None):
+        """img with every foreground pixel set to 0 whose component (label_components' components) has fewer than min_size
+        pixels; every other pixel bit for bit.  A new device array of img's dtype; `out` may name the array to write, `img`
+        itself included.  Stream ordered."""
+        H, W, dtype, flags, min_size = remove_small_params(img, min_size, connectivity, by_value)
+        out = self._cc_out(img, out, img.dtype)
+        if min_size > H * W:                        # no component is that large: every pixel becomes 0
+            L.check(self.lib.ma_memset(self.handle, out.ptr, 0, out.nbytes))
+        elif min_size <= 1:                         # every component is that large
+            if out is not img:
+                L.check(self.lib.ma_memcpy_d2d(self.handle, out.ptr, img.ptr, img.nbytes))
+        else:
+            self._run(self.lib.ma_cc_filter, img.ptr, dtype, H, W, flags, min_size, L.MA_CC_MAX_PIXELS, 0, out.ptr)
+        return out
+
+    def fill_holes(self, img, max_size=None, connectivity=1, value=1, out=None):
+        """img with every enclosed hole set to `value`: a hole is a component of the pixels that are 0, joined under
+        `connectivity`, that has no pixel in the first or last row or column and, with max_size, at most max_size pixels.
+        Every other pixel bit for bit.  A new device array of img's dtype; `out` may name the array to write, `img` itself
+        included.  Stream ordered."""
+        H, W, dtype, flags, max_area, value = fill_holes_params(img, max_size, connectivity, value)
+        out = self._cc_out(img, out, img.dtype)
+        self._run(self.lib.ma_cc_filter, img.ptr, dtype, H, W, flags, 0, max_area, value, out.ptr)
         return out
 
     def flow_refine_step(self, ref, warped, flow, taps, floor, weight=None, max_step=1.0, return_info=False, out=None):
